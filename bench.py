@@ -12,17 +12,30 @@ into the all-reduce buckets, the language bucket started while preprocess_bwd st
 Views shard one per rank (camera yaw depends on the rank), Gaussians are replicated: weak
 scaling.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       N > 1 without WORLD_SIZE in the environment: bench.py starts N ranks itself (a
       torch.distributed.run child, before any GPU call) and exits with its status
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
   python bench.py --gpus 2 --dry-run     # ranks come up on gloo, agree on the world size; no GPU
 
-Rank 0 prints ONE JSON line.  Extra fields: per-stage HIP-event times (stages_ms), the
-roofline of the dominant kernel (SURVEY §8d algorithmic bytes / HIP-event time), whole-step
-algorithmic HBM GB/s, forward FPS at 1.0 Mpix (1280x800, the >=450 FPS target), the quick
-(sparse 192-channel) render + codebook decode FPS at 1 Mpix, and the CPU baseline (the
-oracle's C restatement on the host's cores).
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set up, warm
+up, time the K steps (nothing else in the timed region), write the last timed step's outputs
+if --dump-outputs is given, print metric / value / ms_per_step and the workload description.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed
+(the forward's images and radii, and the gradients the step returns) as DIR/<name>.npy in
+float32, plus DIR/manifest.json (shapes; which arrays are samples).  An array of more than
+DUMP_MAX_ELEMS elements is stored as a fixed seeded sample of its flattened elements.  The
+inputs are seeded, so two builds run with the same arguments compare output for output.
+
+--full adds everything else, each in runs of its own outside the timed steps: per-stage
+HIP-event times (stages_ms), the roofline of the dominant kernel (SURVEY §8d algorithmic
+bytes / HIP-event time; the dominant kernel is then event-bracketed on every ROOF_EVERY-th
+timed step), whole-step algorithmic HBM GB/s, the deterministic backward's cost, forward FPS
+at 1.0 Mpix (1280x800, the >=450 FPS target), the quick (sparse 192-channel) render +
+codebook decode FPS at 1 Mpix, the view-stream line of the forward-only configs, and the CPU
+baseline (the oracle's C restatement on the host's cores).  The --no-* options drop single
+parts of a --full run.
 """
 from __future__ import annotations
 
@@ -298,6 +311,38 @@ def timeit(fn, iters):
     return (time.perf_counter() - t0) / iters
 
 
+DUMP_MAX_ELEMS = 1 << 20   # per array: 4 MiB of float32, so the <= 11 arrays of a step stay below 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor, None skipped) as
+    <dirname>/<name>.npy in float32 (radii are small integers, exact in float32).  An array
+    of more than DUMP_MAX_ELEMS elements is stored as the 1-D sample of its flattened
+    elements at sorted indices drawn by numpy's default_rng(0): the same indices in every
+    run, whatever the build.  manifest.json holds each array's full shape and whether it
+    is a sample."""
+    os.makedirs(dirname, exist_ok=True)
+    manifest = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        sampled = n > DUMP_MAX_ELEMS
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).integers(0, n, size=DUMP_MAX_ELEMS))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float32).cpu().numpy()
+        if not sampled:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        manifest[name] = dict(shape=list(t.shape), source_dtype=str(t.dtype), sampled=sampled,
+                              stored_elements=int(a.size))
+    with open(os.path.join(dirname, "manifest.json"), "w") as f:
+        json.dump(dict(sample="numpy default_rng(0).integers(0, n, DUMP_MAX_ELEMS), sorted, into the flattened array",
+                       max_elements=DUMP_MAX_ELEMS, arrays=manifest), f, indent=1)
+
+
 def fwd_fps(g, dev, sh_degree, D, W=1280, H=800, iters=20):
     cam = make_camera(W, H)
     rs = settings(cam, dev, sh_degree, D > 0)
@@ -484,67 +529,68 @@ def main_forward_replicas(args, world, rank, dev) -> int:
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    _lib.profile_stages(None)
-    _lib.profile_reset()
-    _lib.profile_enable(True)
-    for _ in range(max(2, min(args.steps, 5))):
-        step()
-    torch.cuda.synchronize()
-    _lib.profile_enable(False)
-    per_stage = {k: ms / calls for k, (ms, calls) in _lib.profile_query().items() if calls}
     dom = "render_fwd"
-    _lib.profile_stages([dom])
-    _lib.profile_reset()
-    _lib.profile_enable(True)
-    torch.cuda.synchronize()
+    if args.full:
+        _lib.profile_stages(None)
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        for _ in range(max(2, min(args.steps, 5))):
+            step()
+        torch.cuda.synchronize()
+        _lib.profile_enable(False)
+        per_stage = {k: ms / calls for k, (ms, calls) in _lib.profile_query().items() if calls}
+        _lib.profile_stages([dom])
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
+    last = None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        _lib.profile_enable(i % ROOF_EVERY == 0)   # as in the training bench
-        step()
+        if args.full:
+            _lib.profile_enable(i % ROOF_EVERY == 0)   # as in the training bench
+        if i < args.steps - 1:
+            step()   # its outputs are dropped at once
+        else:
+            last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    _lib.profile_enable(False)
-    _lib.profile_stages(None)
-    dom_ms_s, dom_calls = _lib.profile_query()[dom]
-    # the same forwards over a stream of views, two in flight (view_stream.ViewStream):
-    # reported beside `value`, which is one view at a time
-    from langsplatv2_amd.view_stream import ViewStream
-    vs = ViewStream(dev)
-    for _ in range(3):
-        vs.push(step)
-    vs.flush()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        vs.push(step)
-    vs.flush()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed_stream = time.perf_counter() - t1
+    if args.full:
+        _lib.profile_enable(False)
+        _lib.profile_stages(None)
+        dom_ms_s, dom_calls = _lib.profile_query()[dom]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(color=last[0], language_feature=last[1] if D else None, radii=last[2]))
+    last = None
+    elapsed_stream = 0.0
+    if args.full:
+        # the same forwards over a stream of views, two in flight (view_stream.ViewStream):
+        # reported beside `value`, which is one view at a time
+        from langsplatv2_amd.view_stream import ViewStream
+        vs = ViewStream(dev)
+        for _ in range(3):
+            vs.push(step)
+        vs.flush()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            vs.push(step)
+        vs.flush()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        elapsed_stream = time.perf_counter() - t1
     if world > 1:
         t = torch.tensor([elapsed, elapsed_stream], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)   # timing only, not on the data path
         elapsed, elapsed_stream = float(t[0].item()), float(t[1].item())
     if rank == 0:
-        S = 3 * (deg + 1) ** 2 if deg is not None else 0
-        bytes_, info = algorithmic_bytes(g, rs, D, S)
-        dom_ms = dom_ms_s / dom_calls if dom_calls else 0.0
-        dom_gbps = bytes_[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
         step_ms = elapsed / args.steps * 1e3
-        fwd_keys = ("preprocess", "bin_count", "scan_tile_counts", "bin_scatter", "tile_sort", "render_fwd")
-        pre = f"cfg{args.config}_r"
-        traffic, traffic_src = pmc_traffic(dom, prefix=pre)
-        # §8d charges every instance its 4C-byte feature row (M * 140 B at C = 35), which the
-        # kernel re-reads from L2: the algorithmic rate exceeds the HBM peak, so the HBM
-        # roofline here is the MEASURED traffic (PMC) over the launch time
-        meas_gbps = traffic / (dom_ms * 1e-3) / 1e9 if (traffic and dom_ms > 0) else None
         out = {
             "metric": FWD_METRIC[args.config],
             "value": round(world * args.steps / elapsed, 3),
@@ -564,6 +610,20 @@ def main_forward_replicas(args, world, rank, dev) -> int:
                 "global_batch": world, "parallelism": f"replicas x{world}" if world > 1 else "single GPU",
             },
             "ranks_seen": dist.get_world_size() if world > 1 else 1,
+        }
+    if rank == 0 and args.full:
+        S = 3 * (deg + 1) ** 2 if deg is not None else 0
+        bytes_, info = algorithmic_bytes(g, rs, D, S)
+        dom_ms = dom_ms_s / dom_calls if dom_calls else 0.0
+        dom_gbps = bytes_[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        fwd_keys = ("preprocess", "bin_count", "scan_tile_counts", "bin_scatter", "tile_sort", "render_fwd")
+        pre = f"cfg{args.config}_r"
+        traffic, traffic_src = pmc_traffic(dom, prefix=pre)
+        # §8d charges every instance its 4C-byte feature row (M * 140 B at C = 35), which the
+        # kernel re-reads from L2: the algorithmic rate exceeds the HBM peak, so the HBM
+        # roofline here is the MEASURED traffic (PMC) over the launch time
+        meas_gbps = traffic / (dom_ms * 1e-3) / 1e9 if (traffic and dom_ms > 0) else None
+        out.update({
             "roofline": {
                 "bound": "hbm", "kernel": dom,
                 "achieved": round(meas_gbps, 1) if meas_gbps is not None else None, "peak": HBM_PEAK_GBPS,
@@ -586,10 +646,11 @@ def main_forward_replicas(args, world, rank, dev) -> int:
             "view_stream_fps": round(world * args.steps / elapsed_stream, 3),
             "view_stream_note": "the same forwards over a stream of views, two in flight on alternating "
                                 "HIP streams (langsplatv2_amd.view_stream.ViewStream); `value` is one view at a time",
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cam, gcpu, D, cfg_name=f"cfg{args.config}", backward=False,
                                                tile_sample=FWD_CPU_TILES[args.config])
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
@@ -605,12 +666,19 @@ def main() -> int:
     ap.add_argument("--config", type=int, default=3, choices=[1, 2, 3, 5],
                     help="3: BASELINE cfg3 fwd+bwd (the headline); 1: BASELINE cfg1 fwd+bwd (1k Gaussians, "
                          "128x128, RGB); 2 / 5: BASELINE cfg2 / cfg5 forward-only replicas")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fwd-1mpix", action="store_true")
-    ap.add_argument("--no-quick", action="store_true")
-    ap.add_argument("--no-det", action="store_true", help="skip the deterministic-backward sub-line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-stage times, the roofline, the "
+                         "deterministic backward, forward / quick FPS at 1 Mpix, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fwd-1mpix", action="store_true", help="with --full: skip the forward FPS at 1 Mpix")
+    ap.add_argument("--no-quick", action="store_true", help="with --full: skip the quick render + decode line")
+    ap.add_argument("--no-det", action="store_true", help="with --full: skip the deterministic-backward sub-line")
     ap.add_argument("--dry-run", action="store_true", help="bring the ranks up on gloo and exit (no GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)
@@ -661,8 +729,12 @@ def main() -> int:
     xev = [torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)]
     xms = [0.0, 0]
 
-    def step(timed_exchange=False):
+    fwd_out = {}   # --dump-outputs: the last timed step's forward outputs
+
+    def step(timed_exchange=False, keep_fwd=False):
         color, lang, radii = rast(means3D=g["means3D"], means2D=g["means2D"], opacities=g["opacities"], **kw)
+        if keep_fwd:
+            fwd_out.update(color=color.detach(), language_feature=lang.detach() if D else None, radii=radii)
         if exch is None:
             return torch.autograd.grad(outs_of(color, lang), inputs, grads_in)
         # gradients land in the all-reduce buckets; the language bucket's all-reduce
@@ -683,59 +755,66 @@ def main() -> int:
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # per-stage breakdown (+ the exposed exchange time): a separate untimed pass with every
-    # stage bracketed by events (each bracket idles the stream a few us, so the timed region
-    # below brackets only the dominant stage, for the live roofline)
-    _lib.profile_stages(None)
-    _lib.profile_reset()
-    _lib.profile_enable(True)
-    for _ in range(max(2, min(args.steps, 5))):
-        step(timed_exchange=True)
-    torch.cuda.synchronize()
-    _lib.profile_enable(False)
-    stages = _lib.profile_query()
-    per_stage = {k: dict(ms_per_launch=(ms / calls if calls else 0.0), launches=calls)
-                 for k, (ms, calls) in stages.items() if calls}
-    dom = max(per_stage, key=lambda k: per_stage[k]["ms_per_launch"])
+    # --full: per-stage breakdown (+ the exposed exchange time): a separate untimed pass with
+    # every stage bracketed by events (each bracket idles the stream a few us, so the timed
+    # region below brackets only the dominant stage, for the live roofline); a plain run
+    # times the steps with no event bracket at all
+    if args.full:
+        _lib.profile_stages(None)
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        for _ in range(max(2, min(args.steps, 5))):
+            step(timed_exchange=True)
+        torch.cuda.synchronize()
+        _lib.profile_enable(False)
+        stages = _lib.profile_query()
+        per_stage = {k: dict(ms_per_launch=(ms / calls if calls else 0.0), launches=calls)
+                     for k, (ms, calls) in stages.items() if calls}
+        dom = max(per_stage, key=lambda k: per_stage[k]["ms_per_launch"])
+        if world > 1:
+            dist.barrier()
+        _lib.profile_stages([dom])
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    _lib.profile_stages([dom])
-    _lib.profile_reset()
-    _lib.profile_enable(True)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
+    dump = bool(args.dump_outputs) and rank == 0
+    last = None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        # the dominant kernel is bracketed by events on every ROOF_EVERY-th step
-        # of the timed region (each bracket idles the stream a few us)
-        _lib.profile_enable(i % ROOF_EVERY == 0)
-        step()
+        if args.full:
+            # the dominant kernel is bracketed by events on every ROOF_EVERY-th step
+            # of the timed region (each bracket idles the stream a few us)
+            _lib.profile_enable(i % ROOF_EVERY == 0)
+        if i < args.steps - 1:
+            step()   # its outputs are dropped at once, as a training loop's are
+        else:
+            last = step(keep_fwd=dump)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    _lib.profile_enable(False)
-    _lib.profile_stages(None)
-    dom_ms_s, dom_calls = _lib.profile_query()[dom]
+    if args.full:
+        _lib.profile_enable(False)
+        _lib.profile_stages(None)
+        dom_ms_s, dom_calls = _lib.profile_query()[dom]
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump:
+        # what a caller of the step receives: the forward's outputs and the gradients of
+        # every input (after the all-reduce for N > 1: the leaves' only, in bucket order)
+        names = list(leaf_keys) + ["means2D"] if exch is None else list(leaf_keys)
+        dump_outputs(args.dump_outputs, {**fwd_out, **{"grad_" + k: t for k, t in zip(names, last)}})
+        fwd_out.clear()
+    last = None
 
     if rank == 0:
         frames = world * args.steps
         value = frames / elapsed
-        with torch.no_grad():
-            gd = {k: v.detach() for k, v in g.items()}
-            bytes_, info = algorithmic_bytes(gd, rs, D, 3 * (deg + 1) ** 2 if deg is not None else 0)
-        dom_ms = dom_ms_s / dom_calls if dom_calls else 0.0
-        dom_gbps = bytes_[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        pre = "r" if args.config == 3 else f"cfg{args.config}_r"
-        traffic, traffic_src = pmc_traffic(dom, prefix=pre)
         step_ms = elapsed / args.steps * 1e3
-        kernel_ms = sum(v["ms_per_launch"] for v in per_stage.values())
-        total_bytes = sum(bytes_.values())
         out = {
             "metric": METRIC if args.config == 3 else
             "frames/s fwd+bwd @ 1k Gaussians 128x128 RGB (BASELINE configs[0]); ms_per_step = its fwd+bwd time",
@@ -760,6 +839,18 @@ def main() -> int:
                 if world > 1 else "single GPU",
             },
             "ranks_seen": dist.get_world_size() if world > 1 else 1,
+        }
+    if rank == 0 and args.full:
+        with torch.no_grad():
+            gd = {k: v.detach() for k, v in g.items()}
+            bytes_, info = algorithmic_bytes(gd, rs, D, 3 * (deg + 1) ** 2 if deg is not None else 0)
+        dom_ms = dom_ms_s / dom_calls if dom_calls else 0.0
+        dom_gbps = bytes_[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        pre = "r" if args.config == 3 else f"cfg{args.config}_r"
+        traffic, traffic_src = pmc_traffic(dom, prefix=pre)
+        kernel_ms = sum(v["ms_per_launch"] for v in per_stage.values())
+        total_bytes = sum(bytes_.values())
+        out.update({
             "exchange": ({"bucket_bytes": exch.bucket_bytes, "sh_factored": exch.sh_idx is not None,
                           "early_bucket_bytes": exch.early.nbytes if exch.early is not None else 0,
                           "exposed_ms_per_step": round(xms[0] / max(xms[1], 1), 4),
@@ -796,7 +887,7 @@ def main() -> int:
             "stages_ms": {k: round(v["ms_per_launch"], 4) for k, v in per_stage.items()},
             "stage_bytes": {k: int(v) for k, v in bytes_.items()},
             "workload_stats": info,
-        }
+        })
         if world == 1 and args.config == 3 and not args.no_det:
             out["deterministic"] = deterministic_cost(step, args.steps)
         if world == 1 and not args.no_fwd_1mpix and args.config == 3:
@@ -805,6 +896,7 @@ def main() -> int:
             out["quick_1mpix"] = quick_fps(N, dev)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cam, gcpu, D, cfg_name=f"cfg{args.config}")
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -8,8 +8,8 @@ Steps (run in order; outputs under gpurun_out/, named TAG_*):
     ftests         pytest tests/test_fullsize.py (whole BASELINE frames)
     test:PATH      pytest PATH (one file or node id)
     smoke          __graft_entry__.smoke()
-    bench          python bench.py                       -> TAG_bench.json
-    cfg1 cfg2 cfg5 python bench.py --config N            -> TAG_cfgN.json
+    bench          python bench.py --full                -> TAG_bench.json
+    cfg1 cfg2 cfg5 python bench.py --full --config N     -> TAG_cfgN.json
     prof           rocprofv3 --kernel-trace --stats of the cfg3 step ALONE
                    (bench.py --no-quick --no-fwd-1mpix --no-det --no-cpu-baseline)
                    -> TAG_kernel_stats.md (the roofline cross-check)
@@ -108,9 +108,9 @@ def step(tag, s):
         run([PY, "-u", "-c", "import __graft_entry__ as g; g.smoke()"], 300, log)
         tail(log, 3)
     elif s == "bench":
-        bench(tag, "bench", [])
+        bench(tag, "bench", ["--full"])
     elif s in ("cfg1", "cfg2", "cfg5"):
-        bench(tag, s, ["--config", s[3:]])
+        bench(tag, s, ["--full", "--config", s[3:]])
     elif s == "prof":
         d = rocprof(tag, "prof", None, ["python3", os.path.join(ROOT, "bench.py")] + CFG3_ONLY, limit=300)
         db = next((os.path.join(r, f) for r, _, fs in os.walk(d) for f in fs if f == "run_results.db"), None)
@@ -178,7 +178,8 @@ def step(tag, s):
         env = dict(os.environ, LSR_BENCH_BACKEND="gloo", LSR_BENCH_SAME_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
         with open(js, "w") as f, open(js[:-5] + ".err", "w") as g:
             rc = subprocess.call(["timeout", "-k", "10", "400", PY, "bench.py", "--gpus", "2", "--steps", "5",
-                                  "--warmup", "2", "--no-quick", "--no-fwd-1mpix", "--no-cpu-baseline", "--no-det"],
+                                  "--warmup", "2", "--full", "--no-quick", "--no-fwd-1mpix", "--no-cpu-baseline",
+                                  "--no-det"],
                                  stdout=f, stderr=g, cwd=ROOT, env=env)
         if rc != 0:
             tail(js[:-5] + ".err", 20)
