@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-#define LSR_ABI_VERSION 12  /* 12 (r06): LSR_OPT_DETERMINISTIC;
+#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_quick_query_plan_bytes / _prepare / _run;
+                               12 (r06): LSR_OPT_DETERMINISTIC;
                                11 (r05): LSR_INDEX_PACKED, lsr_quick_pack_codes, LSR_OPT_SPLIT_PREPROCESS;
                                10 (r05): lsr_settings.quick_layout, lsr_quick_decode_run weight_layout;
                                9 (r05): LSR_OPT_LISTS_MAX_MB; LSR_BIN_ORDERED removed */
@@ -261,6 +262,33 @@ size_t lsr_quick_decode_plan_bytes(int L, int K, int Df, int normalize);
 int lsr_quick_decode_prepare(const float* codebooks, int L, int K, int Df, int normalize, void* plan, void* stream);
 int lsr_quick_decode_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int Df, int H,
                          int W, int normalize, float eps, float* out, void* stream);
+
+/* Fused text-query maps of the quick path: what the reference computes from
+ * the decoded, normalised (L, H, W, Df) map with
+ * OpenCLIPNetwork.get_max_across_quick (eval/openclip_encoder.py:114-139;
+ * callers eval_lerf.py:113,160, eval_3d_ovs.py:112,217, demo_prompt.py:122),
+ * taken straight from the weight map — the Df-dim map is never written.
+ * pos (n_pos, Df) and neg (n_neg, Df) are the text embeddings (fp32 device
+ * pointers, used as given: the caller normalises them, as the reference does).
+ * lsr_quick_query_prepare writes the (codebooks, query set) part — the
+ * projections CB_l E^T (512-term dots in f64) as MFMA fragments and the
+ * decode's norm factor — into a caller-owned device buffer of
+ * lsr_quick_query_plan_bytes bytes (0 = unsupported shape), valid until the
+ * codebooks or the embeddings change.  lsr_quick_query_run writes
+ * out (L, n_pos, H, W) fp32 for one frame:
+ *   LSR_QUERY_RELEVANCY  min_j softmax(scale * (sim_pos, sim_neg_j))[0]
+ *                        = 1 / (1 + exp(scale * (max_j sim_neg_j - sim_pos))),
+ *                        scale >= 0 (the reference's is 10), n_neg >= 1;
+ *   LSR_QUERY_COSINE     sim_pos = f . e / (|f| + eps) per level (n_neg may be 0).
+ * K must be 64, Df a multiple of 16, n_pos >= 1, n_pos + n_neg <= 64 per call
+ * (a caller with more positives runs them in chunks); n_pos and n_neg must be
+ * the plan's.  Additive to ABI 12. */
+enum { LSR_QUERY_RELEVANCY = 0, LSR_QUERY_COSINE = 1 };
+size_t lsr_quick_query_plan_bytes(int L, int K, int Df, int n_pos, int n_neg);
+int lsr_quick_query_prepare(const float* codebooks, const float* pos, const float* neg, int L, int K, int Df,
+                            int n_pos, int n_neg, void* plan, void* stream);
+int lsr_quick_query_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int n_pos,
+                        int n_neg, int H, int W, int mode, float scale, float eps, float* out, void* stream);
 
 /* Fused top-k soft codes (replaces softmax_to_topk_soft_code,
  * utils/vq_utils.py:9-24; get_weights_and_indices, :26-40; the per-level

@@ -7,8 +7,9 @@ gaussian_renderer/__init__.py and train.py run unchanged.  Compute is in
 liblsr.so (C ABI: include/lsr.h).
 """
 from ._lib import deterministic, set_deterministic  # noqa: F401
+from .query import QuickRelevancyStream, query_plan, relevancy_maps, similarity_maps  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: F401
                          rasterize_gaussians)
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "deterministic",
-           "set_deterministic"]
+           "set_deterministic", "relevancy_maps", "similarity_maps", "query_plan", "QuickRelevancyStream"]

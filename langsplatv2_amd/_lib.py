@@ -22,6 +22,7 @@ LSR_BUF_GUARD, LSR_BUF_SPARSE, LSR_BUF_GRAD_LANG, LSR_BUF_LISTS, LSR_BUF_DET = 7
 LSR_INDEX_F32, LSR_INDEX_I32, LSR_INDEX_I64, LSR_INDEX_PACKED = 0, 1, 2, 3
 LSR_GWS_GEOM, LSR_GWS_LANG = 1, 2
 LSR_LAYOUT_CHW, LSR_LAYOUT_HWC = 0, 1
+LSR_QUERY_RELEVANCY, LSR_QUERY_COSINE = 0, 1
 
 _vp = ctypes.c_void_p
 
@@ -126,7 +127,8 @@ class BwdOut(ctypes.Structure):
 ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int)
 
 EXPORTS = ("lsr_forward", "lsr_backward", "lsr_mark_visible", "lsr_quick_decode", "lsr_quick_decode_plan_bytes",
-           "lsr_quick_decode_prepare", "lsr_quick_decode_run", "lsr_quick_pack_codes", "lsr_topk_code_forward",
+           "lsr_quick_decode_prepare", "lsr_quick_decode_run", "lsr_quick_query_plan_bytes", "lsr_quick_query_prepare",
+           "lsr_quick_query_run", "lsr_quick_pack_codes", "lsr_topk_code_forward",
            "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_adam_step", "lsr_sh_grad_from_views", "lsr_strerror",
            "lsr_abi_version", "lsr_max_lang_dim", "lsr_profile_enable", "lsr_profile_stages", "lsr_profile_reset",
            "lsr_profile_query", "lsr_set_option", "lsr_get_option", "lsr_stream_create", "lsr_stream_destroy")
@@ -164,6 +166,13 @@ def load(path: str | None = None):
     lib.lsr_quick_decode_run.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp]
     lib.lsr_quick_decode_run.restype = ctypes.c_int
+    lib.lsr_quick_query_plan_bytes.argtypes = [ctypes.c_int] * 5
+    lib.lsr_quick_query_plan_bytes.restype = ctypes.c_size_t
+    lib.lsr_quick_query_prepare.argtypes = [_vp, _vp, _vp] + [ctypes.c_int] * 5 + [_vp, _vp]
+    lib.lsr_quick_query_prepare.restype = ctypes.c_int
+    lib.lsr_quick_query_run.argtypes = [_vp, ctypes.c_int, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float,
+                                                                                      _vp, _vp]
+    lib.lsr_quick_query_run.restype = ctypes.c_int
     if hasattr(lib, "lsr_stream_create"):      # (older A/B builds lack it)
         lib.lsr_stream_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
         lib.lsr_stream_create.restype = ctypes.c_int

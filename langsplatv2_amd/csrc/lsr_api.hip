@@ -362,6 +362,44 @@ int lsr_quick_decode_run(const float* weight_map, int weight_layout, const void*
     return LSR_OK;
 }
 
+size_t lsr_quick_query_plan_bytes(int L, int K, int Df, int n_pos, int n_neg)
+{
+    if (L < 0 || K != 64 || Df <= 0 || (Df % 16) != 0 || n_pos < 1 || n_neg < 0 || n_pos + n_neg > 64) return 0;
+    return lsr::quick_query_plan_bytes(L, K, n_pos, n_neg);
+}
+
+int lsr_quick_query_prepare(const float* codebooks, const float* pos, const float* neg, int L, int K, int Df,
+                            int n_pos, int n_neg, void* plan, void* stream)
+{
+    if (L < 0 || Df <= 0 || (Df % 16) != 0 || n_pos < 1 || n_neg < 0) return LSR_EINVAL;
+    if (K != 64 || n_pos + n_neg > 64) return LSR_EUNSUPPORTED;
+    if (L == 0) return LSR_OK;
+    if (!codebooks || !pos || (n_neg > 0 && !neg) || !plan) return LSR_EINVAL;
+    if (lsr::launch_quick_query_prepare(codebooks, pos, neg, L, K, Df, n_pos, n_neg, plan, (hipStream_t)stream) !=
+        hipSuccess)
+        return LSR_EHIP;
+    return LSR_OK;
+}
+
+int lsr_quick_query_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int n_pos,
+                        int n_neg, int H, int W, int mode, float scale, float eps, float* out, void* stream)
+{
+    if (L < 0 || H < 0 || W < 0 || n_pos < 1 || n_neg < 0) return LSR_EINVAL;
+    if (weight_layout != LSR_LAYOUT_CHW && weight_layout != LSR_LAYOUT_HWC) return LSR_EINVAL;
+    if (mode != LSR_QUERY_RELEVANCY && mode != LSR_QUERY_COSINE) return LSR_EINVAL;
+    // min_j softmax = sigmoid(scale (sim_pos - max_j sim_neg_j)) needs scale >= 0
+    if (mode == LSR_QUERY_RELEVANCY && !(scale >= 0.f)) return LSR_EINVAL;
+    if (K != 64 || n_pos + n_neg > 64 || (mode == LSR_QUERY_RELEVANCY && n_neg < 1)) return LSR_EUNSUPPORTED;
+    if (L == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!weight_map || !plan || !out) return LSR_EINVAL;
+    // the pixel-major map is read in 16-B pieces
+    if (weight_layout == LSR_LAYOUT_HWC && ((uintptr_t)weight_map % 16) != 0) return LSR_EUNSUPPORTED;
+    if (lsr::launch_quick_query_run(weight_map, weight_layout == LSR_LAYOUT_HWC, plan, L, K, n_pos, n_neg, H, W,
+                                    mode == LSR_QUERY_RELEVANCY, scale, eps, out, (hipStream_t)stream) != hipSuccess)
+        return LSR_EHIP;
+    return LSR_OK;
+}
+
 static int lang_loss_args(const float* wm, const float* cb, int K, int Df, int H, int W, const int32_t* seg,
                           const float* feat, int S)
 {

@@ -181,6 +181,12 @@ hipError_t launch_quick_decode_run(const float* wmap, const float* cb, int L, in
                                    bool hwc = false);
 hipError_t launch_quick_decode(const float* wmap, const float* cb, int L, int K, int Df, int H, int W, int normalize,
                                float eps, void* ws, float* out, hipStream_t st);
+// fused text-query relevancy / cosine maps (K = 64, n_pos + n_neg <= 64)
+size_t quick_query_plan_bytes(int L, int K, int n_pos, int n_neg);
+hipError_t launch_quick_query_prepare(const float* cb, const float* pos, const float* neg, int L, int K, int Df,
+                                      int n_pos, int n_neg, void* ws, hipStream_t st);
+hipError_t launch_quick_query_run(const float* wmap, bool hwc, const void* ws, int L, int K, int n_pos, int n_neg,
+                                  int H, int W, bool relevancy, float scale, float eps, float* out, hipStream_t st);
 
 // lang_loss.hip
 size_t lang_loss_workspace_bytes(int S, int W, int H, int* waves);

@@ -462,9 +462,94 @@ __device__ __forceinline__ void dec_swap_lanebit(f32x4q& X, f32x4q& Y)
     }
 }
 
+// The tile front end of k_quick_decode_l as functions, for k_quick_query
+// (k_quick_decode_l keeps its inlined copy: calling these changed its generated
+// code, and its instruction stream is what the decode's timings were taken on).
+// Raw weights of 64-pixel tile tt of level l (a tile past the last reads tile 0 and
+// gives zeros): lane (li, lg) holds raw[pb][s][j] = W[64 l + 32 s + 8 lg + j][x = bx + 16 pb + li].
 // HWC: the weight map is pixel-major (H, W, lk) (LSR_LAYOUT_HWC): a lane's 8 codes
 // of one pixel are 32 contiguous bytes, two 16-B loads instead of eight 4-B ones
 // from eight channel planes.
+template <bool HWC>
+__device__ __forceinline__ void dec_load_tile(float (&raw)[4][2][8], const float* __restrict__ wmap, int tt, int ntile,
+                                              int nbx, int W, size_t HW, int l, int lk, int li, int lg)
+{
+    const bool ok = tt < ntile;
+    const int tq = ok ? tt : 0;
+    const int bx = (tq % nbx) * 64, y = tq / nbx;
+#pragma unroll
+    for (int pb = 0; pb < 4; pb++) {
+        const int xa = bx + 16 * pb + li;
+        const size_t pa = (size_t)y * W + min(xa, W - 1);
+        const bool in = ok && xa < W;
+        if constexpr (HWC) {
+            const float4* wp = reinterpret_cast<const float4*>(wmap + pa * lk + l * 64 + 8 * lg);
+#pragma unroll
+            for (int s2 = 0; s2 < 2; s2++) {
+                const float4 v0 = wp[8 * s2], v1 = wp[8 * s2 + 1];
+                raw[pb][s2][0] = in ? v0.x : 0.f;
+                raw[pb][s2][1] = in ? v0.y : 0.f;
+                raw[pb][s2][2] = in ? v0.z : 0.f;
+                raw[pb][s2][3] = in ? v0.w : 0.f;
+                raw[pb][s2][4] = in ? v1.x : 0.f;
+                raw[pb][s2][5] = in ? v1.y : 0.f;
+                raw[pb][s2][6] = in ? v1.z : 0.f;
+                raw[pb][s2][7] = in ? v1.w : 0.f;
+            }
+        } else {
+#pragma unroll
+            for (int s2 = 0; s2 < 2; s2++)
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const float v = wmap[(size_t)(l * 64 + 32 * s2 + 8 * lg + j) * HW + pa];
+                    raw[pb][s2][j] = in ? v : 0.f;
+                }
+        }
+    }
+}
+
+// Per-pixel power-of-two scaling of a tile's weights, then the f16 split: the
+// pixel's largest |w| goes to [0.5, 1), so a nearly transparent pixel's small
+// weights keep all 22 bits of hi + lo instead of falling into f16's subnormal
+// range (exact: the caller undoes the scale, and the L2 norm is scale-
+// invariant).  Lane (li, lg) holds pixel (pb, li); psc[pb] = 2^e of that
+// pixel: w = psc * w_scaled.
+__device__ __forceinline__ void dec_scale_split(float (&raw)[4][2][8], float (&psc)[4], h8 (&Wh)[4][2], h8 (&Wl)[4][2])
+{
+#pragma unroll
+    for (int pb = 0; pb < 4; pb++) {
+        float m = 0.f;
+#pragma unroll
+        for (int s2 = 0; s2 < 2; s2++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) m = fmaxf(m, fabsf(raw[pb][s2][j]));
+        m = fmaxf(m, __shfl_xor(m, 16, 64));
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        int e = 0;
+        if (m > 0.f && m < 3.0e38f) (void)frexpf(m, &e);
+        // both factors stay finite normals: a subnormal m (e down to -148)
+        // or m >= 2^127 would otherwise make inv or psc infinite
+        e = min(max(e, -126), 126);
+        psc[pb] = ldexpf(1.f, e);
+        const float inv = ldexpf(1.f, -e);
+#pragma unroll
+        for (int s2 = 0; s2 < 2; s2++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) raw[pb][s2][j] *= inv;
+    }
+#pragma unroll
+    for (int pb = 0; pb < 4; pb++)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; s2++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const float v = raw[pb][s2][j];
+                const _Float16 h = (_Float16)v;
+                Wh[pb][s2][j] = h;
+                Wl[pb][s2][j] = (_Float16)(v - (float)h);
+            }
+}
+
 template <bool NORM, bool VEC, bool HWC = false>
 __global__ void __launch_bounds__(64 * LSR_DEC2_WAVES, 1)
     k_quick_decode_l(const float* __restrict__ wmap, int Df, int W, int H, const uint4* __restrict__ frag,
@@ -694,6 +779,21 @@ size_t quick_decode_workspace_bytes(int L, int K, int Df, int normalize)
 #endif
 }
 
+// The norm factor of every level: Gram matrix G (L, K, K) -> its Cholesky factor
+// Lf (L, K, K) -> the factor's fragments + scales (chol), or the Gram matrices'
+// own fragments (!chol: what k_quick_decode_h reads).
+static void norm_factor_prepare(const float* cb, int L, int K, int Df, float* G, float* Lf, uint4* nfrag,
+                                float* nscales, bool chol, hipStream_t st)
+{
+    k_codebook_gram_t<<<dim3((unsigned)((K / 16) * (K / 16)), (unsigned)L), 256, 0, st>>>(cb, K, Df, G);
+    if (chol) {
+        k_codebook_chol<<<L, 256, 0, st>>>(G, K, Lf);
+        k_codebook_frag<<<L, 256, 0, st>>>(Lf, K, K, nfrag, nscales);
+    } else {
+        k_codebook_frag<<<L, 256, 0, st>>>(G, K, K, nfrag, nscales);
+    }
+}
+
 // The plan (= the workspace): codebook fragments + scales, and with
 // normalisation the Gram matrices, their Cholesky factors and the factors'
 // fragments + scales (for Df > 512 the Gram matrices' fragments instead).
@@ -717,17 +817,24 @@ hipError_t launch_quick_decode_prepare(const float* cb, int L, int K, int Df, in
         float* Lf = G + (size_t)L * K * K;
         uint4* nfrag = (uint4*)(Lf + (size_t)L * K * K);
         float* nscales = (float*)((uint8_t*)nfrag + (size_t)L * 64 * 256);
-        k_codebook_gram_t<<<dim3((unsigned)((K / 16) * (K / 16)), (unsigned)L), 256, 0, st>>>(cb, K, Df, G);
 #ifndef LSR_DECODE_H
-        if (Df / 16 <= LSR_DEC2_MAXDB) {
-            k_codebook_chol<<<L, 256, 0, st>>>(G, K, Lf);
-            k_codebook_frag<<<L, 256, 0, st>>>(Lf, K, K, nfrag, nscales);
-        } else
+        norm_factor_prepare(cb, L, K, Df, G, Lf, nfrag, nscales, Df / 16 <= LSR_DEC2_MAXDB, st);
+#else
+        norm_factor_prepare(cb, L, K, Df, G, Lf, nfrag, nscales, false, st);
 #endif
-            k_codebook_frag<<<L, 256, 0, st>>>(G, K, K, nfrag, nscales);
     }
 #endif
     return hipGetLastError();
+}
+
+static int cu_count()
+{
+    static int ncu = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n > 0 ? n : 256;
+    }();
+    return ncu;
 }
 
 hipError_t launch_quick_decode_run(const float* wmap, const float* cb, int L, int K, int Df, int H, int W,
@@ -751,11 +858,7 @@ hipError_t launch_quick_decode_run(const float* wmap, const float* cb, int L, in
 #ifndef LSR_DECODE_H
     if (NDB <= LSR_DEC2_MAXDB) {
         // level-resident: one workgroup per CU, the CUs split evenly over the levels
-        static int ncu = [] {
-            int dev = 0, n = 256;
-            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            return n > 0 ? n : 256;
-        }();
+        const int ncu = cu_count();
         const int nwg = ncu / L > 0 ? ncu / L : 1;
         const size_t lds = (size_t)(NDB + (normalize ? 4 : 0)) * 256 * sizeof(uint4);
         auto run = [&](auto kern) {
@@ -806,6 +909,258 @@ hipError_t launch_quick_decode(const float* wmap, const float* cb, int L, int K,
     const hipError_t e = launch_quick_decode_prepare(cb, L, K, Df, normalize, ws, st);
     if (e != hipSuccess) return e;
     return launch_quick_decode_run(wmap, cb, L, K, Df, H, W, normalize, eps, ws, out, st);
+}
+
+// ---------------------------------------------------------------------------
+// Fused text-query relevancy (replaces, after the decode above, the reference's
+// OpenCLIPNetwork.get_max_across_quick, eval/openclip_encoder.py:114-139).  The
+// (L, Df, H, W) feature map never exists: with pixel weights w (K), codebook
+// CB_l (K x Df) and a unit text embedding e,
+//   f . e = w^T (CB_l e)            one column of P_l = CB_l E^T (K x (N_neg + Q)), per query set
+//   |f|   = |L_l^T w|               the decode's Cholesky norm factor
+//   sim   = f . e / (|f| + eps)
+// and the reference's softmax over (10 sim_pos, 10 sim_neg_j) followed by the
+// min over j is 1 / (1 + exp(scale (max_j sim_neg_j - sim_pos))) for scale >= 0.
+// Per pixel and level: one K x (64 + 16 NCB) product on the decode's A
+// fragments, 768 B read, 4 Q B written.
+
+// P[l][k][c] = sum_d CB[l][k][d] E[c][d], the 512-term dot in f64; columns: the
+// n_neg negatives, then the n_pos positives, then zeros up to ncp (a multiple of 16).
+__global__ void __launch_bounds__(256) k_query_project(const float* __restrict__ cb, const float* __restrict__ pos,
+                                                       const float* __restrict__ neg, int K, int Df, int n_pos,
+                                                       int n_neg, int ncp, float* __restrict__ P)
+{
+    const int l = blockIdx.y;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= K * ncp) return;
+    const int k = idx / ncp, c = idx % ncp;
+    double s = 0.0;
+    if (c < n_neg + n_pos) {
+        const float* a = cb + ((size_t)l * K + k) * Df;
+        const float* e = c < n_neg ? neg + (size_t)c * Df : pos + (size_t)(c - n_neg) * Df;
+        for (int d = 0; d < Df; d++) s += (double)a[d] * (double)e[d];
+    }
+    P[(size_t)l * K * ncp + idx] = (float)s;
+}
+
+// 16-lane max (every lane of each 16-lane row gets its row's maximum)
+__device__ __forceinline__ float row16_max(float v)
+{
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false)));
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false)));
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false)));
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false)));
+    return v;
+}
+
+// Level-resident like k_quick_decode_l: the level's NCB projection blocks and the
+// 4 norm-factor blocks (4 KB each) stay in LDS, a wave takes 64-pixel tiles with
+// the next tile's weights in flight.  A product block leaves its 16 columns
+// across a row's 16 lanes (lane li = column, registers = pixels 4 lg + r), so
+// the maximum over the negative columns is a masked 16-lane reduction; blocks
+// 0 .. (n_neg - 1) / 16 hold negatives and are reduced first, the last of them
+// (which may also hold positives) stays in registers for the output pass.
+// REL: out (L, n_pos, H, W) = relevancy; else the cosine similarities of the positives.
+template <bool REL, bool VEC, bool HWC>
+__global__ void __launch_bounds__(64 * LSR_DEC2_WAVES, 1)
+    k_quick_query(const float* __restrict__ wmap, int W, int H, const uint4* __restrict__ pfrag,
+                  const float* __restrict__ pscales, const uint4* __restrict__ nfrag,
+                  const float* __restrict__ nscales, float* __restrict__ out, float eps, float scale, int nwg, int lk,
+                  int n_pos, int n_neg, int NCB)
+{
+    extern __shared__ uint4 sfr[];   // [cb][s][lane][hi, lo] projection, then 4 blocks of the norm factor
+    const int l = (int)blockIdx.x / nwg, wi = (int)blockIdx.x % nwg;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, lg = lane >> 4, li = lane & 15;
+    {
+        const uint4* src = pfrag + (size_t)l * NCB * 256;
+        for (int i = threadIdx.x; i < NCB * 256; i += 64 * LSR_DEC2_WAVES) sfr[i] = src[i];
+        const uint4* ns = nfrag + (size_t)l * 4 * 256;
+        for (int i = threadIdx.x; i < 4 * 256; i += 64 * LSR_DEC2_WAVES) sfr[NCB * 256 + i] = ns[i];
+    }
+    __syncthreads();
+    const float sc = pscales[l];
+    const float ns2 = nscales[l] * nscales[l];
+    const size_t HW = (size_t)W * H;
+    const int nbx = (W + 63) / 64;
+    const int ntile = nbx * H;
+    const int stride = nwg * LSR_DEC2_WAVES;
+    const int nbn = (n_neg + 15) >> 4;   // blocks holding negatives
+    const int cb0 = n_neg >> 4;          // the first block holding a positive
+    float raw[4][2][8];
+    int t = wi * LSR_DEC2_WAVES + w;
+    dec_load_tile<HWC>(raw, wmap, t, ntile, nbx, W, HW, l, lk, li, lg);
+    for (; t < ntile; t += stride) {
+        const int bx = (t % nbx) * 64, y = t / nbx;
+        float psc[4];
+        h8 Wh[4][2], Wl[4][2];
+        dec_scale_split(raw, psc, Wh, Wl);   // sim is invariant to the scale but for eps (below)
+        dec_load_tile<HWC>(raw, wmap, t + stride, ntile, nbx, W, HW, l, lk, li, lg);
+        // Y^T = W^T L: lane (k = 16 mb + li, lg) gets Y[k] of pixels 4 lg + r; |f|^2 = sum_k Y[k]^2
+        float sq[4][4];
+#pragma unroll
+        for (int pb = 0; pb < 4; pb++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) sq[pb][r] = 0.f;
+#pragma unroll 1
+        for (int mb = 0; mb < 4; mb++) {
+            const uint4* f = sfr + (size_t)(NCB + mb) * 256 + lane * 2;
+            const h8 c0h = __builtin_bit_cast(h8, f[0]), c0l = __builtin_bit_cast(h8, f[1]);
+            const h8 c1h = __builtin_bit_cast(h8, f[128]), c1l = __builtin_bit_cast(h8, f[129]);
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++) {
+                f32x4q acc = {0.f, 0.f, 0.f, 0.f};
+                LSR_DEC_MFMA6(acc, pb);
+#pragma unroll
+                for (int r = 0; r < 4; r++) sq[pb][r] = fmaf(acc[r], acc[r], sq[pb][r]);
+            }
+        }
+        // sim = (w . P) / (|f| + eps) with both products taken on the scaled weights
+        // w / osc: eps becomes eps / osc, exactly as in the decode (osc is a power of
+        // two within the normal range, so the product with 1 / osc has the quotient's bits)
+        float mul[4][4];
+#pragma unroll
+        for (int pb = 0; pb < 4; pb++) {
+            const float ipsc = 1.f / psc[pb];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float iosc = __shfl(ipsc, 4 * lg + r, 64);
+                mul[pb][r] = sc / (sqrtf(fmaxf(row16_sum(sq[pb][r]) * ns2, 0.f)) + eps * iosc);
+            }
+        }
+        f32x4q v[4];
+        auto sims = [&](int cb) {
+            const uint4* f = sfr + (size_t)cb * 256 + lane * 2;
+            const h8 c0h = __builtin_bit_cast(h8, f[0]), c0l = __builtin_bit_cast(h8, f[1]);
+            const h8 c1h = __builtin_bit_cast(h8, f[128]), c1l = __builtin_bit_cast(h8, f[129]);
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++) {
+                f32x4q acc = {0.f, 0.f, 0.f, 0.f};
+                LSR_DEC_MFMA6(acc, pb);
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[pb][r] = acc[r] * mul[pb][r];
+            }
+        };
+        float mneg[4][4];
+        if constexpr (REL) {
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) mneg[pb][r] = -INFINITY;
+#pragma unroll 1
+            for (int cb = 0; cb < nbn; cb++) {
+                sims(cb);
+                const bool isneg = 16 * cb + li < n_neg;
+#pragma unroll
+                for (int pb = 0; pb < 4; pb++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        mneg[pb][r] = fmaxf(mneg[pb][r], row16_max(isneg ? v[pb][r] : -INFINITY));
+            }
+        }
+#pragma unroll 1
+        for (int cb = cb0; cb < NCB; cb++) {
+            if (!REL || cb >= nbn) sims(cb);   // block nbn - 1 is still in v
+            const int q = 16 * cb + li - n_neg;
+            const bool isq = q >= 0 && q < n_pos;   // else a negative's or a padding column's lane
+            float* const orow = out + ((size_t)l * n_pos + (isq ? q : 0)) * HW + (size_t)y * W;
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++) {
+                if (!isq) continue;
+                float o4[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    // (v_rcp_f32: 1 ulp, and exact for the all-zero pixel's 1 / 2)
+                    if constexpr (REL) o4[r] = __builtin_amdgcn_rcpf(1.f + expf(scale * (mneg[pb][r] - v[pb][r])));
+                    else o4[r] = v[pb][r];
+                }
+                const int xo = bx + 16 * pb + 4 * lg;
+                float* o = orow + xo;
+                if (VEC && xo + 3 < W) {
+                    *reinterpret_cast<float4*>(o) = make_float4(o4[0], o4[1], o4[2], o4[3]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        if (xo + r < W) o[r] = o4[r];
+                }
+            }
+        }
+    }
+}
+
+// The query plan: projection fragments (L x NCB x 4 KB) + scales, the norm
+// factor chain of the decode plan (Gram matrices, Cholesky factors, the
+// factors' fragments + scales), and the f32 projection the fragments are packed from.
+struct QueryPlan {
+    uint4* pfrag;
+    float* pscales;
+    float* G;
+    float* Lf;
+    uint4* nfrag;
+    float* nscales;
+    float* P;
+    size_t bytes;
+};
+
+static QueryPlan query_plan_layout(void* ws, int L, int K, int ncp)
+{
+    auto up = [](size_t n) { return (n + 255) / 256 * 256; };
+    const uintptr_t p = (uintptr_t)ws;   // (nullptr: only .bytes is used)
+    QueryPlan q;
+    size_t o = 0;
+    q.pfrag = (uint4*)(p + o);   o += (size_t)L * (ncp / 16) * 4096;
+    q.pscales = (float*)(p + o); o += up((size_t)L * 4);
+    q.G = (float*)(p + o);       o += (size_t)L * K * K * 4;
+    q.Lf = (float*)(p + o);      o += (size_t)L * K * K * 4;
+    q.nfrag = (uint4*)(p + o);   o += (size_t)L * 4 * 4096;
+    q.nscales = (float*)(p + o); o += up((size_t)L * 4);
+    q.P = (float*)(p + o);       o += up((size_t)L * K * ncp * 4);
+    q.bytes = o;
+    return q;
+}
+
+static int query_ncp(int n_pos, int n_neg) { return (n_pos + n_neg + 15) / 16 * 16; }
+
+size_t quick_query_plan_bytes(int L, int K, int n_pos, int n_neg)
+{
+    return query_plan_layout(nullptr, L, K, query_ncp(n_pos, n_neg)).bytes;
+}
+
+hipError_t launch_quick_query_prepare(const float* cb, const float* pos, const float* neg, int L, int K, int Df,
+                                      int n_pos, int n_neg, void* ws, hipStream_t st)
+{
+    if (L == 0) return hipSuccess;
+    const int ncp = query_ncp(n_pos, n_neg);
+    const QueryPlan q = query_plan_layout(ws, L, K, ncp);
+    k_query_project<<<dim3((unsigned)((K * ncp + 255) / 256), (unsigned)L), 256, 0, st>>>(cb, pos, neg, K, Df, n_pos,
+                                                                                        n_neg, ncp, q.P);
+    k_codebook_frag<<<L, 256, 0, st>>>(q.P, K, ncp, q.pfrag, q.pscales);
+    norm_factor_prepare(cb, L, K, Df, q.G, q.Lf, q.nfrag, q.nscales, true, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_quick_query_run(const float* wmap, bool hwc, const void* ws, int L, int K, int n_pos, int n_neg,
+                                  int H, int W, bool relevancy, float scale, float eps, float* out, hipStream_t st)
+{
+    if (L == 0 || H == 0 || W == 0) return hipSuccess;
+    const int ncp = query_ncp(n_pos, n_neg);
+    const QueryPlan q = query_plan_layout(const_cast<void*>(ws), L, K, ncp);
+    const bool vec = (W % 4) == 0 && ((uintptr_t)out % 16) == 0;
+    const int ncu = cu_count();
+    const int nwg = ncu / L > 0 ? ncu / L : 1;
+    const int NCB = ncp / 16;
+    const size_t lds = (size_t)(NCB + 4) * 256 * sizeof(uint4);
+    auto run = [&](auto kern) {
+        kern<<<(unsigned)(nwg * L), 64 * LSR_DEC2_WAVES, lds, st>>>(wmap, W, H, q.pfrag, q.pscales, q.nfrag, q.nscales,
+                                                                  out, eps, scale, nwg, L * K, n_pos, n_neg, NCB);
+    };
+    if (relevancy) {
+        if (hwc) { if (vec) run(k_quick_query<true, true, true>); else run(k_quick_query<true, false, true>); }
+        else     { if (vec) run(k_quick_query<true, true, false>); else run(k_quick_query<true, false, false>); }
+    } else {
+        if (hwc) { if (vec) run(k_quick_query<false, true, true>); else run(k_quick_query<false, false, true>); }
+        else     { if (vec) run(k_quick_query<false, true, false>); else run(k_quick_query<false, false, false>); }
+    }
+    return hipGetLastError();
 }
 
 }  // namespace lsr

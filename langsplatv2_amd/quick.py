@@ -26,6 +26,14 @@ from . import _lib
 from .rasterizer import _stream
 
 
+def _is_pixel_major(weight_map: torch.Tensor) -> bool:
+    """An fp32 (D, H, W) view of a pixel-major (H, W, D) buffer, 16-B aligned: the
+    rasterizer's language_feature_layout="hwc" output, read as it is (LSR_LAYOUT_HWC)."""
+    D, H, W = weight_map.shape
+    return (weight_map.dtype == torch.float32 and weight_map.stride() == (1, D * W, D)
+            and weight_map.data_ptr() % 16 == 0 and H * W > 1)
+
+
 def decode_language_features(weight_map: torch.Tensor, codebooks: torch.Tensor, normalize: bool = True,
                              eps: float = 1e-10, out: torch.Tensor | None = None) -> torch.Tensor:
     """weight_map (L*K, H, W) fp32 CUDA, codebooks (L, K, Df) fp32 CUDA ->
@@ -43,8 +51,7 @@ def decode_language_features(weight_map: torch.Tensor, codebooks: torch.Tensor, 
         raise RuntimeError("decode_language_features: tensors must be on the ROCm device (there is no CPU path)")
     if K != 64 or Df % 16 != 0:
         raise ValueError("decode_language_features: K must be 64 and Df a multiple of 16")
-    hwc = (weight_map.dtype == torch.float32 and weight_map.stride() == (1, D * W, D) and Df <= 512
-           and weight_map.data_ptr() % 16 == 0 and H * W > 1)
+    hwc = _is_pixel_major(weight_map) and Df <= 512
     wm = weight_map if hwc else weight_map.contiguous().float()
     cb = codebooks.contiguous().float()
     if out is None:
@@ -91,7 +98,56 @@ def decode_plan(codebooks: torch.Tensor, normalize: bool = True) -> torch.Tensor
     return plan
 
 
-class QuickFeatureStream:
+class _OverlapStream:
+    """Render on the caller's stream, the per-frame consumer kernel on a second
+    (non-blocking) HIP stream: frame i's result comes back from the push of
+    frame i + 1 (or from `flush`), made safe to use on the caller's stream.
+    Subclasses give `_alloc(wm)` (the output tensor for a weight map) and
+    `_run(wm, out)` (enqueue the consumer on the current stream)."""
+
+    def __init__(self, device):
+        from ._lib import nonblocking_stream
+        self._device = device
+        self._decode_stream = nonblocking_stream(device)   # no implicit sync with the default stream
+        self._pending = None
+
+    def push(self, render_fn) -> torch.Tensor | None:
+        """Render one view on the caller's current stream (render_fn returns its
+        (L*K, H, W) weight map) and queue its consumer; returns the previous
+        view's result, or None for the first view."""
+        with torch.no_grad():
+            wm = render_fn()
+        cur = torch.cuda.current_stream(wm.device)
+        rendered = torch.cuda.Event()
+        rendered.record(cur)
+        prev = self._take(cur)   # the caller's stream waits for the previous frame's kernel only now
+        # the output is allocated on the caller's stream (where it is used and freed) and
+        # kept from reuse until the side stream has written it
+        out = self._alloc(wm)
+        with torch.cuda.stream(self._decode_stream):
+            self._decode_stream.wait_event(rendered)
+            self._run(wm, out)
+            done = torch.cuda.Event()
+            done.record(self._decode_stream)
+        wm.record_stream(self._decode_stream)    # the map stays allocated until its consumer ran
+        out.record_stream(self._decode_stream)
+        self._pending = (out, done)
+        return prev
+
+    def flush(self) -> torch.Tensor | None:
+        """The last pushed view's result (None if there is none pending)."""
+        return self._take(torch.cuda.current_stream(self._device))
+
+    def _take(self, cur):
+        if self._pending is None:
+            return None
+        out, done = self._pending
+        self._pending = None
+        cur.wait_event(done)
+        return out
+
+
+class QuickFeatureStream(_OverlapStream):
     """Render + decode over a stream of views, frame i's decode overlapping
     frame i+1's render.  The reference evaluates view after view, each as
     render -> einsum -> normalise (eval_lerf.py:210-220, :320-350;
@@ -111,49 +167,19 @@ class QuickFeatureStream:
         use(fs.flush())
 
     Each frame's values equal decode_language_features(weight map) exactly (the
-    same kernels; only the issue order differs)."""
+    same kernels; only the issue order differs).  A caller that wants text-query
+    relevancy maps, not the features, uses query.QuickRelevancyStream."""
 
     def __init__(self, codebooks: torch.Tensor, normalize: bool = True, eps: float = 1e-10):
+        super().__init__(codebooks.device)
         self.codebooks, self.normalize, self.eps = codebooks, bool(normalize), float(eps)
-        from ._lib import nonblocking_stream
-        self._decode_stream = nonblocking_stream(codebooks.device)   # no implicit sync with the default stream
-        self._pending = None
 
-    def push(self, render_fn) -> torch.Tensor | None:
-        """Render one view on the caller's current stream (render_fn returns its
-        (L*K, H, W) weight map) and queue its decode; returns the previous
-        view's features, or None for the first view."""
-        with torch.no_grad():
-            wm = render_fn()
-        cur = torch.cuda.current_stream(wm.device)
-        rendered = torch.cuda.Event()
-        rendered.record(cur)
-        prev = self._take(cur)   # the caller's stream waits for the previous decode only now
-        # the output is allocated on the caller's stream (where it is used and freed) and
-        # kept from reuse until the decode stream has written it
+    def _alloc(self, wm):
         L, _, Df = self.codebooks.shape
-        out = torch.empty((L, Df) + tuple(wm.shape[1:]), dtype=torch.float32, device=wm.device)
-        with torch.cuda.stream(self._decode_stream):
-            self._decode_stream.wait_event(rendered)
-            decode_language_features(wm, self.codebooks, self.normalize, self.eps, out=out)
-            decoded = torch.cuda.Event()
-            decoded.record(self._decode_stream)
-        wm.record_stream(self._decode_stream)    # the map stays allocated until its decode ran
-        out.record_stream(self._decode_stream)
-        self._pending = (out, decoded)
-        return prev
+        return torch.empty((L, Df) + tuple(wm.shape[1:]), dtype=torch.float32, device=wm.device)
 
-    def flush(self) -> torch.Tensor | None:
-        """The last pushed view's features (None if there is none pending)."""
-        return self._take(torch.cuda.current_stream(self.codebooks.device))
-
-    def _take(self, cur):
-        if self._pending is None:
-            return None
-        out, decoded = self._pending
-        self._pending = None
-        cur.wait_event(decoded)
-        return out
+    def _run(self, wm, out):
+        decode_language_features(wm, self.codebooks, self.normalize, self.eps, out=out)
 
 
 def compute_final_feature_map(weight_map: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
