@@ -547,7 +547,7 @@ static std::atomic<int64_t> g_lists_max_mb{2048};
 // with the binning (preprocess.hip k_preprocess_colour).
 static std::atomic<int64_t> g_split_pre{1};
 // LSR_OPT_DETERMINISTIC: the render backward's cross-block sums as 64-bit
-// fixed-point atomics (render.hip det_shift), converted back by k_det_finish
+// fixed-point atomics (render_det.h det_shift), converted back by k_det_finish
 static std::atomic<int64_t> g_det{0};
 #ifndef LSR_SPLIT_MIN_P
 #define LSR_SPLIT_MIN_P (1 << 19)
@@ -1036,7 +1036,7 @@ int lsr_forward(const lsr_settings* s, const lsr_inputs* in, lsr_fwd_out* out, l
                 ra.zero2_n16 = bytes / 16;
             }
             out->grad_ws_kind = w.kind;
-            // the backward's per-block candidate lists (render.hip LST): the render
+            // the backward's per-block candidate lists (render_fwd.hip ZERO / render_bwd.hip LST): the render
             // writes each 8x8 block's staged candidates; capacity 4 entries per instance
             const size_t L = block_lists_bytes((size_t)M, (size_t)T);
             if (L && L <= ((size_t)g_lists_max_mb.load(std::memory_order_relaxed) << 20)) {

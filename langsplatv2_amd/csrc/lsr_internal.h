@@ -68,7 +68,8 @@ hipError_t launch_tile_sort(int T, const uint32_t* tile_start, uint64_t* keys, u
                             uint32_t* cls_cnt, uint32_t* cls_list, const uint32_t* host_cnt, hipStream_t st);
 
 
-// render.hip
+// render_fwd.hip, render_quick.hip (the forward render; RenderArgs is also the
+// backward's view of the forward, RenderBwdArgs::f)
 struct RenderArgs {
     Cam cam;
     int P;
@@ -104,6 +105,11 @@ struct RenderArgs {
     const uint4* border = nullptr;   // {block 4 tile + sub, tile_start[tile], tile_start[tile + 1], lcount[block]}
 };
 hipError_t launch_render_fwd(const RenderArgs& a, hipStream_t st);
+// its quick arm (a.qw set, at least one tile): render_quick.hip
+hipError_t launch_render_fwd_quick(const RenderArgs& a, hipStream_t st);
+int lang_set_for(int D);     // compiled channel set >= D, or -1
+
+// render_bwd.hip
 // the backward's block order (RenderArgs::border, 4 T entries) from the forward's lcount
 #ifndef LSR_BWD_ORDER
 #define LSR_BWD_ORDER 1   // list-driven backward: heaviest block lists dispatched first (0: band order)
@@ -130,7 +136,7 @@ struct RenderBwdArgs {
     float* qw_acc = nullptr;
     // LSR_OPT_DETERMINISTIC: the atomics add 64-bit fixed-point twins of grad_acc
     // (det_rows, same (P, VP) indexing) and lang_acc (det_lang, (P, D)), each value
-    // scaled by 2^det_shift(...) (render.hip); det_bounds = {max |dL/dout|,
+    // scaled by 2^det_shift(...) (render_det.h); det_bounds = {max |dL/dout|,
     // max |feature|, flag bits} from launch_det_bounds, radii the forward's
     long long* det_rows = nullptr;
     long long* det_lang = nullptr;
@@ -150,7 +156,8 @@ hipError_t launch_render_bwd_lang(const RenderBwdArgs& a, hipStream_t st);
 // language-only backward of the quick (sparse) input: a.qw_acc (P, K) from
 // the Dq-channel gradient (Dq must be a compiled channel set, <= 64)
 hipError_t launch_render_bwd_lang_sparse(const RenderBwdArgs& a, hipStream_t st);
-int lang_set_for(int D);     // compiled channel set >= D, or -1
+
+// render_det.hip
 // LSR_OPT_DETERMINISTIC: bounds = {max |dL/dout| over the 3 + D planes,
 // max |feature| over the visible Gaussians' colours and the dense language input,
 // flag} (flag bit 0: a non-finite value).  bounds points at LSR_DET_HDR bytes:

@@ -277,7 +277,7 @@ def _packed_codes(qi: torch.Tensor, Dq: int) -> torch.Tensor:
 
 def _use_packed(qw: torch.Tensor, qi: torch.Tensor, Dq: int) -> bool:
     """The packed rows apply: 12 codes per Gaussian, Dq <= 192, 16-B aligned rows
-    (the LDS-DMA quick kernel, csrc/render.hip k_render_fwd_quick_d)."""
+    (the LDS-DMA quick kernel, csrc/render_quick.hip k_render_fwd_quick_d)."""
     return (QUICK_PACKED_CODES and qi.dim() == 2 and qi.shape[0] > 0 and qi.shape[1] == 12 and qw.shape[1] == 12
             and Dq <= 192 and qi.dtype in (torch.float32, torch.int32, torch.int64)
             and qw.data_ptr() % 16 == 0 and qi.data_ptr() % 16 == 0)

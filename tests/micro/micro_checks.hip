@@ -164,7 +164,7 @@ extern "C" int micro_mfma_order(int R, int seed, int specials, long long* counts
     return 0;
 }
 
-// The render backward's fast exponential (v_exp_f32 of power * log2 e, render.hip
+// The render backward's fast exponential (v_exp_f32 of power * log2 e, render_bwd.hip
 // k_render_bwd_mf phase 1) against the deterministic expf_det the forward and
 // the oracle use, EXHAUSTIVELY over every float power in [lo, 0]: the largest
 // relative difference |e_hw - e_det| / e_det.  The backward's alpha band

@@ -1,4 +1,4 @@
-"""The list-driven backward's dispatch order (render.hip k_bwd_order,
+"""The list-driven backward's dispatch order (render_bwd.hip k_bwd_order,
 RenderArgs::border, ImageLayout::border).
 
 A training forward ends by sorting the 8x8 blocks of each XCD dispatch range

@@ -1,4 +1,4 @@
-"""The deterministic backward (LSR_OPT_DETERMINISTIC, include/lsr.h; render.hip
+"""The deterministic backward (LSR_OPT_DETERMINISTIC, include/lsr.h; render_det.h
 det_shift / k_det_finish): bit-reproducible gradients, compared with the oracle
 at tolerances DERIVED from an error analysis, not fitted to measurements.
 
@@ -62,7 +62,7 @@ def _frexp_e(x):
 
 def _quant(radii, cls, Dm, Am, WH):
     """nb 2^-(s+1): the fixed-point rounding of one element's block partials
-    (render.hip det_shift restated; x2 margin for the fp32 evaluation of the
+    (render_det.h det_shift restated; x2 margin for the fp32 evaluation of the
     exponent's inputs)."""
     rr = np.maximum(radii, 1).astype(np.float32)
     q = np.float32(0.25) * rr + np.float32(2.0)

@@ -25,6 +25,8 @@ CASES = {
     # language blocks mask the channels past D
     "sh2_lang24_ragged": dict(N=6000, W=136, H=100, sh_degree=2, lang_dim=24, bg=(0.2, 0.1, 0.7), seed=10),
     "lang48": dict(N=4000, W=112, H=96, sh_degree=3, lang_dim=48, seed=11),
+    # and below the 16-channel set: the masked D = 16 forward, the D < 16 backward over set 16
+    "lang12": dict(N=3000, W=96, H=80, sh_degree=2, lang_dim=12, seed=12),
 }
 
 
@@ -91,7 +93,7 @@ def test_backward_vs_oracle(name, gpu, oracle_lib):
 def test_block_list_chunk_boundaries(N, gpu, oracle_lib):
     """One 16x16 tile (four 8x8 blocks) at D = 16: the backward reads each
     block's candidate list in chunks of one 16-candidate group
-    (render.hip LSR_LST_CHUNK) with a counted DMA wait, so list lengths below,
+    (render_bwd.hip LSR_LST_CHUNK) with a counted DMA wait, so list lengths below,
     at and across multiples of 16 (and a lone candidate) must give the
     oracle's gradients."""
     case = make_case(N=N, W=16, H=16, sh_degree=None, lang_dim=16, seed=40 + N)

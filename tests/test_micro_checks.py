@@ -51,7 +51,7 @@ def test_mfma_f32_is_an_in_order_fmaf_chain(micro, specials):
 def test_fast_exp_inside_the_backward_alpha_band(micro):
     """The render backward evaluates G with the hardware v_exp_f32 (power * log2 e)
     and re-takes the alpha >= 1/255 decision with expf_det (the forward's, the
-    oracle's) for every lane whose alpha is within 2e-8 of 1/255 (render.hip,
+    oracle's) for every lane whose alpha is within 2e-8 of 1/255 (render_bwd.hip,
     k_render_bwd_mf phase 1).  That is exact only if the two exponentials differ
     by less than 2e-8 * 255 = 5.1e-6 relative wherever alpha can reach 1/255:
     powers >= ln(1/255) - ln(opacity), i.e. >= -5.55 for opacities <= 1

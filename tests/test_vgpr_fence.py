@@ -1,5 +1,5 @@
 """The quick render kernels keep each pixel's 192 channel sums in v64..v255
-and limit the compiler to v0..v62 (amdgpu_num_vgpr(63), csrc/render.hip); the
+and limit the compiler to v0..v62 (amdgpu_num_vgpr(63), csrc/render_quick.hip); the
 compiler can overrun that limit silently under register pressure.  The built
 library's gfx950 code object is disassembled and every instruction outside the
 kernels' inline asm must stay below v63 (tools/check_vgpr_fence.py)."""

@@ -1,5 +1,5 @@
 """The quick render register-fence checker (tools/check_vgpr_fence.py, run by
-__graft_entry__.build()) accepts only the inline-asm forms render.hip emits:
+__graft_entry__.build()) accepts only the inline-asm forms render_quick.hip emits:
 synthetic disassembly lines a compiler-made overrun would produce are rejected
 (the store forms used to be accepted whatever their operands)."""
 import os

@@ -3,7 +3,7 @@
 k_render_fwd_quick_v / _d keep the pixel's 192 channel sums in v64..v255
 (v63 = the junk channel) and are compiled with amdgpu_num_vgpr(63), so the
 compiler's own code must stay in v0..v62; only the kernels' inline asm may
-touch v63 and above (csrc/render.hip: the index-mode zeroing, update and read,
+touch v63 and above (csrc/render_quick.hip: the index-mode zeroing, update and read,
 and the two epilogues).  The attribute is a limit the compiler can overrun
 without a diagnostic when register pressure rises (a hoisted-load variant
 allocated v58..v72 and overwrote channels 0..8), so this disassembles the
@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 HI = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 
-# the inline-asm forms allowed to name v63 and above (render.hip); each form also
+# the inline-asm forms allowed to name v63 and above (render_quick.hip); each form also
 # pins which operands may be high: addresses and offsets below v63, data only in
 # the channel registers v64..v255 (a compiler-made store with a spilled address
 # or data in the fence, the overrun this tool exists to catch, is rejected)

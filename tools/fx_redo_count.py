@@ -1,4 +1,4 @@
-"""Census of the fast-exp forward's exact re-renders (render.hip FX): with the
+"""Census of the fast-exp forward's exact re-renders (render_fwd.hip FX, tools/variants/fwd_fast_exp.patch): with the
 variant built by
   python tools/variant.py fxmark 'if (FX && !exact && redo != 0u) continue;' 'const bool mark = ...'
 (lane 0 of a block whose termination test fell in the error band stores

@@ -28,7 +28,8 @@ V = {
 }
 # candidate: the ML forward's gathered language slices (A operand) loaded one 4-candidate step ahead
 V["fwdpf"] = [(
-    """            for (int q0 = 0; q0 < n; q0 += 4) {
+    """            int q0 = 0;
+            for (; q0 < nproc; q0 += 4) {
                 if (wave_ballot(!done) == 0) break;
                 // A operand: language channel 16 nb + li of candidate q0 + lg
                 // (0 past the chunk) -- from the staged rows, or (SF) gathered
@@ -57,13 +58,14 @@ V["fwdpf"] = [(
                 }
             };
             float avn[MLB];
-            if (n > 0) a_op(0, avn);
-            for (int q0 = 0; q0 < n; q0 += 4) {
+            if (nproc > 0) a_op(0, avn);
+            int q0 = 0;
+            for (; q0 < nproc; q0 += 4) {
                 if (wave_ballot(!done) == 0) break;
                 float av[MLB];
 #pragma unroll
                 for (int nb = 0; nb < MLB; nb++) av[nb] = avn[nb];
-                if (q0 + 4 < n) a_op(q0 + 4, avn);""")]
+                if (q0 + 4 < nproc) a_op(q0 + 4, avn);""")]
 
 # baseline: no per-block candidate lists (the backward re-stages from the tile lists)
 V["nolst"] = [("    uint8_t* p = (uint8_t*)lb;\n    ra.listA = (float4*)p;",

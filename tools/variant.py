@@ -4,7 +4,8 @@ sources stay free of experiment switches).
     python tools/variant.py NAME 'old text' 'new text' [file.hip] [-- 'old2' 'new2' [file2]] ...
     python tools/variant.py NAME --patch tools/variants/X.patch [--patch ...] [-- 'old' 'new' ...]
 
-Each replacement must match exactly once in its file (default render.hip).
+Each replacement must match exactly once: in the named file, or, with no file
+named, in the one file of csrc that holds the text.
 Output: langsplatv2_amd/_build/var_NAME/liblsr.so (sources + objects under var_NAME/pkg) (load with tools/ab.py NAME=path)."""
 import os
 import shutil
@@ -39,12 +40,13 @@ def main():
                 subprocess.run(["patch", "-s", "-p3", "-d", src, "-i", os.path.abspath(pf)], check=True)
             continue
         old, new = g[0], g[1]
-        fn = g[2] if len(g) > 2 else "render.hip"
-        p = os.path.join(src, fn)
+        names = [g[2]] if len(g) > 2 else sorted(os.listdir(src))
+        hits = {fn: open(os.path.join(src, fn)).read().count(old) for fn in names}
+        if sum(hits.values()) != 1:
+            where = ", ".join(f"{fn}: {n}" for fn, n in hits.items() if n) or (g[2] if len(g) > 2 else "csrc")
+            raise SystemExit(f"pattern matches {sum(hits.values())} times ({where}): {old[:80]!r}")
+        p = os.path.join(src, max(hits, key=hits.get))
         s = open(p).read()
-        n = s.count(old)
-        if n != 1:
-            raise SystemExit(f"{fn}: pattern matches {n} times: {old[:80]!r}")
         open(p, "w").write(s.replace(old, new))
     subprocess.run(["make", "-s", "-j", "8", "-C", src], check=True)
     out = os.path.join(dst, "liblsr.so")
