@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_quick_query_plan_bytes / _prepare / _run;
+#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_query_post_workspace_bytes, lsr_query_smooth, lsr_query_mask;
+                               12, additive (no bump): lsr_quick_query_plan_bytes / _prepare / _run;
                                12 (r06): LSR_OPT_DETERMINISTIC;
                                11 (r05): LSR_INDEX_PACKED, lsr_quick_pack_codes, LSR_OPT_SPLIT_PREPROCESS;
                                10 (r05): lsr_settings.quick_layout, lsr_quick_decode_run weight_layout;
@@ -289,6 +290,41 @@ int lsr_quick_query_prepare(const float* codebooks, const float* pos, const floa
                             int n_pos, int n_neg, void* plan, void* stream);
 int lsr_quick_query_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int n_pos,
                         int n_neg, int H, int W, int mode, float scale, float eps, float* out, void* stream);
+
+/* Post-process of the relevancy maps (eval_lerf.py:104-200; eval_3d_ovs.py:
+ * 102-107, 215-260) on planes = L * n_prompt independent (H, W) fp32 planes
+ * (level-major: plane = l * n_prompt + q), in two passes with caller-owned
+ * outputs and a caller-owned workspace of lsr_query_post_workspace_bytes bytes
+ * (0 = unsupported shape: more than 65535 planes or 32-row tile rows, or
+ * H * W >= 2^31).  Nothing is synchronised, every result is bit-identical from
+ * run to run, and rel is never written.
+ *
+ * lsr_query_smooth: avg = AvgPool2d(kernel, stride 1, padding (kernel - 1) / 2,
+ * count_include_pad=False)(rel) as row sums then column sums of at most
+ * `kernel` terms each, divided by the in-image tap count; blend =
+ * 0.5 (avg + rel).  avg and blend are optional (NULL: not written).  Per plane
+ * stats (planes, 3) = {min blend, max blend, max avg} and loc (planes, 2) =
+ * {row-major index of the first pixel attaining max avg, number of pixels
+ * attaining it}.  kernel odd, 1..63.
+ *
+ * lsr_query_mask: o = clip(2 ((blend - min) / (max - min + 1e-9f)) - 1, 0, 1)
+ * with min, max from stats; raw = o > thresh; mask (planes, H, W) uint8 = 1
+ * where more than half of the in-image pixels of the smooth_kernel^2 window are
+ * set in raw (integer arithmetic; smooth_kernel odd, 1..15).  counts
+ * (planes, 3) = {set pixels, intersection, union} with the annotation mask
+ * gt_masks (n_prompt, H, W) uint8 (non-zero = inside) of the plane's prompt
+ * (NULL: intersection and union are 0); masked_sum (planes) = sum of blend over
+ * the mask.
+ *
+ * LSR_EINVAL: an even or non-positive kernel, a NULL required pointer, planes
+ * not a multiple of n_prompt; LSR_EUNSUPPORTED: kernel size or shape out of
+ * range; planes, H or W = 0: LSR_OK with nothing launched.  Additive to ABI 12. */
+size_t lsr_query_post_workspace_bytes(int planes, int H, int W);
+int lsr_query_smooth(const float* rel, int planes, int H, int W, int kernel, float* avg, float* blend, float* stats,
+                     int64_t* loc, void* workspace, void* stream);
+int lsr_query_mask(const float* blend, const float* stats, const uint8_t* gt_masks, int planes, int n_prompt, int H,
+                   int W, float thresh, int smooth_kernel, uint8_t* mask, int64_t* counts, float* masked_sum,
+                   void* workspace, void* stream);
 
 /* Fused top-k soft codes (replaces softmax_to_topk_soft_code,
  * utils/vq_utils.py:9-24; get_weights_and_indices, :26-40; the per-level

@@ -10,6 +10,9 @@ from ._lib import deterministic, set_deterministic  # noqa: F401
 from .query import QuickRelevancyStream, query_plan, relevancy_maps, similarity_maps  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: F401
                          rasterize_gaussians)
+from .segment import (LocalizeResult, SegmentResult, hits, localize_maps, segment_maps,  # noqa: F401
+                      smooth_maps)
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "deterministic",
-           "set_deterministic", "relevancy_maps", "similarity_maps", "query_plan", "QuickRelevancyStream"]
+           "set_deterministic", "relevancy_maps", "similarity_maps", "query_plan", "QuickRelevancyStream",
+           "smooth_maps", "segment_maps", "localize_maps", "hits", "SegmentResult", "LocalizeResult"]

@@ -128,7 +128,8 @@ ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c
 
 EXPORTS = ("lsr_forward", "lsr_backward", "lsr_mark_visible", "lsr_quick_decode", "lsr_quick_decode_plan_bytes",
            "lsr_quick_decode_prepare", "lsr_quick_decode_run", "lsr_quick_query_plan_bytes", "lsr_quick_query_prepare",
-           "lsr_quick_query_run", "lsr_quick_pack_codes", "lsr_topk_code_forward",
+           "lsr_quick_query_run", "lsr_query_post_workspace_bytes", "lsr_query_smooth", "lsr_query_mask",
+           "lsr_quick_pack_codes", "lsr_topk_code_forward",
            "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_adam_step", "lsr_sh_grad_from_views", "lsr_strerror",
            "lsr_abi_version", "lsr_max_lang_dim", "lsr_profile_enable", "lsr_profile_stages", "lsr_profile_reset",
            "lsr_profile_query", "lsr_set_option", "lsr_get_option", "lsr_stream_create", "lsr_stream_destroy")
@@ -173,6 +174,12 @@ def load(path: str | None = None):
     lib.lsr_quick_query_run.argtypes = [_vp, ctypes.c_int, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float,
                                                                                       _vp, _vp]
     lib.lsr_quick_query_run.restype = ctypes.c_int
+    lib.lsr_query_post_workspace_bytes.argtypes = [ctypes.c_int] * 3
+    lib.lsr_query_post_workspace_bytes.restype = ctypes.c_size_t
+    lib.lsr_query_smooth.argtypes = [_vp] + [ctypes.c_int] * 4 + [_vp] * 6
+    lib.lsr_query_smooth.restype = ctypes.c_int
+    lib.lsr_query_mask.argtypes = [_vp, _vp, _vp] + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_int] + [_vp] * 5
+    lib.lsr_query_mask.restype = ctypes.c_int
     if hasattr(lib, "lsr_stream_create"):      # (older A/B builds lack it)
         lib.lsr_stream_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
         lib.lsr_stream_create.restype = ctypes.c_int

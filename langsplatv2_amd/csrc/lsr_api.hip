@@ -400,6 +400,39 @@ int lsr_quick_query_run(const float* weight_map, int weight_layout, const void* 
     return LSR_OK;
 }
 
+size_t lsr_query_post_workspace_bytes(int planes, int H, int W)
+{
+    return lsr::query_post_workspace_bytes(planes, H, W);
+}
+
+int lsr_query_smooth(const float* rel, int planes, int H, int W, int kernel, float* avg, float* blend, float* stats,
+                     int64_t* loc, void* workspace, void* stream)
+{
+    if (planes < 0 || H < 0 || W < 0 || kernel < 1 || (kernel & 1) == 0) return LSR_EINVAL;
+    if (kernel > 63 || !lsr::query_post_shape_ok(planes, H, W)) return LSR_EUNSUPPORTED;
+    if (planes == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!rel || !stats || !loc || !workspace) return LSR_EINVAL;
+    if (lsr::launch_query_smooth(rel, planes, H, W, (kernel - 1) / 2, avg, blend, stats, loc, workspace,
+                                 (hipStream_t)stream) != hipSuccess)
+        return LSR_EHIP;
+    return LSR_OK;
+}
+
+int lsr_query_mask(const float* blend, const float* stats, const uint8_t* gt_masks, int planes, int n_prompt, int H,
+                   int W, float thresh, int smooth_kernel, uint8_t* mask, int64_t* counts, float* masked_sum,
+                   void* workspace, void* stream)
+{
+    if (planes < 0 || H < 0 || W < 0 || smooth_kernel < 1 || (smooth_kernel & 1) == 0) return LSR_EINVAL;
+    if (gt_masks && (n_prompt < 1 || planes % n_prompt != 0)) return LSR_EINVAL;
+    if (smooth_kernel > 15 || !lsr::query_post_shape_ok(planes, H, W)) return LSR_EUNSUPPORTED;
+    if (planes == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!blend || !stats || !mask || !counts || !masked_sum || !workspace) return LSR_EINVAL;
+    if (lsr::launch_query_mask(blend, stats, gt_masks, planes, n_prompt, H, W, thresh, (smooth_kernel - 1) / 2, mask,
+                               counts, masked_sum, workspace, (hipStream_t)stream) != hipSuccess)
+        return LSR_EHIP;
+    return LSR_OK;
+}
+
 static int lang_loss_args(const float* wm, const float* cb, int K, int Df, int H, int W, const int32_t* seg,
                           const float* feat, int S)
 {

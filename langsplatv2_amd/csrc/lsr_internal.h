@@ -195,6 +195,19 @@ hipError_t launch_quick_query_prepare(const float* cb, const float* pos, const f
 hipError_t launch_quick_query_run(const float* wmap, bool hwc, const void* ws, int L, int K, int n_pos, int n_neg,
                                   int H, int W, bool relevancy, float scale, float eps, float* out, hipStream_t st);
 
+// query_post.hip: smoothing, masks and localisation of (planes, H, W) relevancy maps
+bool query_post_shape_ok(int planes, int H, int W);
+size_t query_post_workspace_bytes(int planes, int H, int W);
+// box mean of radius r (avg, blend optional), then per plane stats (planes, 3) =
+// {min blend, max blend, max avg} and loc (planes, 2) = {first row-major pixel of max avg, ties}
+hipError_t launch_query_smooth(const float* rel, int planes, int H, int W, int r, float* avg, float* blend,
+                               float* stats, int64_t* loc, void* ws, hipStream_t st);
+// thresholded, majority-smoothed (radius s) masks of blend normalised by stats; counts (planes, 3) =
+// {area, intersection, union with gt[plane % n_prompt] (0 without gt)}, masked_sum (planes)
+hipError_t launch_query_mask(const float* blend, const float* stats, const uint8_t* gt, int planes, int n_prompt,
+                             int H, int W, float thresh, int s, uint8_t* mask, int64_t* counts, float* masked_sum,
+                             void* ws, hipStream_t st);
+
 // lang_loss.hip
 size_t lang_loss_workspace_bytes(int S, int W, int H, int* waves);
 // gw == nullptr: forward (loss and/or the per-pixel stats (2, H, W));
