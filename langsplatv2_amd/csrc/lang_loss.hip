@@ -21,7 +21,7 @@
 //                                  Q    = sum_p beta_p w_p w_p^T.
 // The two K x K x pixels products (G W and the beta-weighted Gram Q) run on
 // exact-f32 MFMA (v_mfma_f32_16x16x4_f32) with the weight tile held in
-// registers in the MFMA output layout (the quick.hip K-order trick), the
+// registers in the MFMA output layout (the K-order trick of the first, exact-f32 quick decode), the
 // segment sums U are run-length accumulated per wave and flushed with
 // atomics when the segment changes.  Traffic: the weight map once
 // (forward), the weight map + the gradient map once (backward).

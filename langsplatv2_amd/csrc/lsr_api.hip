@@ -356,8 +356,8 @@ int lsr_quick_decode_run(const float* weight_map, int weight_layout, const void*
     if (!weight_map || !plan || !out) return LSR_EINVAL;
     // the pixel-major map is read in 32-B pieces by the level-resident kernel (Df <= 512)
     if (weight_layout == LSR_LAYOUT_HWC && (Df > 512 || ((uintptr_t)weight_map % 16) != 0)) return LSR_EUNSUPPORTED;
-    if (lsr::launch_quick_decode_run(weight_map, nullptr, L, K, Df, H, W, normalize, eps, plan, out,
-                                     (hipStream_t)stream, weight_layout == LSR_LAYOUT_HWC) != hipSuccess)
+    if (lsr::launch_quick_decode_run(weight_map, L, K, Df, H, W, normalize, eps, plan, out, (hipStream_t)stream,
+                                     weight_layout == LSR_LAYOUT_HWC) != hipSuccess)
         return LSR_EHIP;
     return LSR_OK;
 }

@@ -6,7 +6,24 @@
 #include "../../include/lsr.h"
 #include "lsr_device.h"
 
+#include <type_traits>
+
 namespace lsr {
+
+// Host dispatch: the launchers pick a kernel instantiation from runtime values
+// (the render's integer helpers: render_common.h).
+// f(std::bool_constant<b>...) for the runtime bools b...
+template <class F>
+void with_bools(F&& f)
+{
+    f();
+}
+template <class F, class... Bs>
+void with_bools(F&& f, bool b, Bs... rest)
+{
+    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
 
 struct Cam {
     int W, H, gx, gy;
@@ -172,23 +189,33 @@ hipError_t launch_det_bounds(const RenderBwdArgs& b, float* bounds, hipStream_t 
 hipError_t launch_det_finish(const RenderBwdArgs& b, bool lang_only, float* grad_out, float* lang_out,
                              hipStream_t st);
 
-// quick.hip
+// lang_codes.hip
 hipError_t launch_topk_code_fwd(const float* logits, int64_t N, int L, int K, int k, float* dense, float* sw,
                                 void* sidx, int idx_dtype, int level_offset, hipStream_t st);
 // sparse: g is dL/dweights of the packed (N, L*k) form (ascending channel order)
 hipError_t launch_topk_code_bwd(const float* logits, const float* g, int64_t N, int L, int K, int k, float* dlogits,
                                 hipStream_t st, bool sparse = false);
+// knn.hip
 size_t knn_workspace_bytes(int64_t N, size_t sort_temp);
 hipError_t knn_sort_temp_bytes(int64_t N, size_t* bytes);
 hipError_t launch_knn_dist2(const float* points, int64_t N, float* out, uint8_t* ws, size_t sort_temp, hipStream_t st);
+
+// quick_decode.hip: codebook decode of the quick language map (K = 64, Df % 16 == 0)
 size_t quick_decode_workspace_bytes(int L, int K, int Df, int normalize);
 hipError_t launch_quick_decode_prepare(const float* cb, int L, int K, int Df, int normalize, void* ws, hipStream_t st);
-hipError_t launch_quick_decode_run(const float* wmap, const float* cb, int L, int K, int Df, int H, int W,
-                                   int normalize, float eps, const void* ws, float* out, hipStream_t st,
-                                   bool hwc = false);
+hipError_t launch_quick_decode_run(const float* wmap, int L, int K, int Df, int H, int W, int normalize, float eps,
+                                   const void* ws, float* out, hipStream_t st, bool hwc = false);
 hipError_t launch_quick_decode(const float* wmap, const float* cb, int L, int K, int Df, int H, int W, int normalize,
                                float eps, void* ws, float* out, hipStream_t st);
-// fused text-query relevancy / cosine maps (K = 64, n_pos + n_neg <= 64)
+// the plan pieces the query plan shares: split-f16 fragments + per-level scales of
+// (L, K, Df) matrices, and the norm factor of every level: Gram matrix G (L, K, K)
+// -> its Cholesky factor Lf (L, K, K) -> the factor's fragments + scales (chol),
+// or the Gram matrices' own fragments (!chol)
+void launch_codebook_frag(const float* cb, int L, int K, int Df, uint4* frag, float* scales, hipStream_t st);
+void norm_factor_prepare(const float* cb, int L, int K, int Df, float* G, float* Lf, uint4* nfrag, float* nscales,
+                         bool chol, hipStream_t st);
+
+// quick_query.hip: fused text-query relevancy / cosine maps (K = 64, n_pos + n_neg <= 64)
 size_t quick_query_plan_bytes(int L, int K, int n_pos, int n_neg);
 hipError_t launch_quick_query_prepare(const float* cb, const float* pos, const float* neg, int L, int K, int Df,
                                       int n_pos, int n_neg, void* ws, hipStream_t st);

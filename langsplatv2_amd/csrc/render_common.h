@@ -154,17 +154,6 @@ bool with_lang_set(int nl, F&& f)
     return with_int<MIN>(LangSets{}, nl, f);
 }
 
-// f(std::bool_constant<b>...) for the runtime bools b...
-template <class F>
-void with_bools(F&& f)
-{
-    f();
-}
-template <class F, class... Bs>
-void with_bools(F&& f, bool b, Bs... rest)
-{
-    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
-    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
-}
+// (with_bools, for runtime bools: lsr_internal.h)
 
 }  // namespace lsr

@@ -9,7 +9,7 @@ callers eval_lerf.py:113,160, eval_3d_ovs.py:112,217, demo_prompt.py:122):
     softmax(10 * stack([pos, neg_j]))[..., 0].min over j  ->  (L, Q, H, W)
 
 `relevancy_maps` computes the same values from the weight map in one HIP
-kernel per frame (csrc/quick.hip, k_quick_query) without the Df-dim map ever
+kernel per frame (csrc/quick_query.hip, k_quick_query) without the Df-dim map ever
 existing: per level f . e = w^T (CB e), |f| = |L^T w| with the Cholesky factor
 of the codebook Gram matrix, and the 2-way softmax + min over the negatives is
 sigmoid(scale * (sim_pos - max_j sim_neg_j)).  Everything that depends only on

@@ -11,7 +11,7 @@ and, for the dense training/eval map, compute_final_feature_map
 (scene/gaussian_model.py:545-550): codebooks.view(-1, Df).T @ W.
 
 `decode_language_features` does both in one HIP kernel per frame
-(csrc/quick.hip: split-f16 MFMA with f32 accumulation, per-pixel norms from
+(csrc/quick_decode.hip: split-f16 MFMA with f32 accumulation, per-pixel norms from
 the Cholesky factor of the codebook Gram matrix, each output written once);
 the codebook-only preparation is cached per codebook tensor (`decode_plan`).
 There is no CPU path.

@@ -1,5 +1,5 @@
 """Fused text-query relevancy / cosine maps of the quick path
-(langsplatv2_amd.query, csrc/quick.hip k_quick_query) against the reference's
+(langsplatv2_amd.query, csrc/quick_query.hip k_quick_query) against the reference's
 OpenCLIPNetwork.get_max_across_quick (eval/openclip_encoder.py:114-139) applied
 to the float64 decode of the weight map (eval_lerf.py:214-218).
 
@@ -139,6 +139,7 @@ def test_abi_status_codes_without_device():
     assert lib.lsr_quick_query_plan_bytes(3, 64, 500, 3, 4) == 0
     assert lib.lsr_quick_query_plan_bytes(3, 64, 512, 61, 4) == 0
     assert lib.lsr_quick_query_plan_bytes(3, 64, 512, 3, 4) >= 3 * (1 + 4) * 4096
+    assert lib.lsr_quick_query_plan_bytes(3, 64, 512, 4, 4) == 172544   # the plan's size is part of the ABI
     run = lib.lsr_quick_query_run
     assert run(None, 0, None, 3, 64, 3, 4, 8, 8, 0, f(10), f(1e-10), None, None) == 1        # null map
     assert run(None, 2, None, 3, 64, 3, 4, 8, 8, 0, f(10), f(1e-10), None, None) == 1        # no such layout

@@ -1,4 +1,4 @@
-"""Codebook decode of the quick language map (langsplatv2_amd.quick, csrc/quick.hip)
+"""Codebook decode of the quick language map (langsplatv2_amd.quick, csrc/quick_decode.hip)
 against a float64 restatement of the reference's post-render lines
 (eval_lerf.py:214-218: einsum('ldk,lkn->ldn') then / (norm + 1e-10); and
 scene/gaussian_model.py:545-550 for the unnormalised dense map).
@@ -37,6 +37,16 @@ def test_validation_on_cpu():
         quick.decode_language_features(torch.zeros(192, 4, 4), torch.zeros(3, 64, 512))
 
 
+@pytest.mark.parametrize("args,nbytes", [((3, 64, 512, 1), 541184), ((3, 64, 512, 0), 393472),
+                                         ((1, 64, 16, 1), 53760), ((2, 64, 1024, 1), 623104)])
+def test_plan_bytes_on_cpu(args, nbytes):
+    """The decode plan's size is part of the ABI (callers own the buffer): fragments
+    L * Df * 256 B + 256 B of scales, and with normalisation 2 L K K f32 (Gram
+    matrices, Cholesky factors) + L * 16 KB of norm fragments + 256 B of scales."""
+    from langsplatv2_amd import _lib
+    assert _lib.load().lsr_quick_decode_plan_bytes(*args) == nbytes
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("H,W", [(37, 45), (64, 128), (1, 1)])
 def test_decode_matches_float64(gpu, H, W):
@@ -48,6 +58,29 @@ def test_decode_matches_float64(gpu, H, W):
     got = quick.decode_language_features(torch.from_numpy(wmap).to(gpu), torch.from_numpy(cb).to(gpu))
     ref = ref_decode(wmap, cb)
     np.testing.assert_allclose(got.cpu().numpy(), ref, atol=DEC_ATOL, rtol=0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", [(3, 70), (2, 72)])
+def test_decode_wide_codebook_fallback(gpu, H, W):
+    """Df > 512 (528: the first size past the level-resident kernel's LDS budget)
+    goes to k_quick_decode_h, channel-major map only.  (3, 70): W % 4 != 0, the
+    scalar-store arm, two 64-pixel tiles per row, the second partial; (2, 72):
+    the 16-B store arm with a partial tile.  That kernel has no per-pixel
+    scaling, so every pixel gets one code of at least 0.25 per level."""
+    g = np.random.default_rng(H * 1000 + W)
+    L, K, Df = 2, 64, 528
+    wmap = (g.random((L * K, H, W)) * (g.random((L * K, H, W)) < 0.15)).astype(np.float32)
+    wmap.reshape(L, K, H, W)[:, 0] = (0.25 + 0.75 * g.random((L, H, W))).astype(np.float32)
+    cb = g.standard_normal((L, K, Df)).astype(np.float32)
+    wm_d, cb_d = torch.from_numpy(wmap).to(gpu), torch.from_numpy(cb).to(gpu)
+    got = quick.decode_language_features(wm_d, cb_d)
+    assert got.shape == (L, Df, H, W)
+    np.testing.assert_allclose(got.cpu().numpy(), ref_decode(wmap, cb), atol=DEC_ATOL, rtol=0)
+    raw = quick.decode_language_features(wm_d, cb_d, normalize=False)
+    ref = ref_decode(wmap, cb, normalize=False)
+    scale = np.abs(ref).max()
+    np.testing.assert_allclose(raw.cpu().numpy() / scale, ref / scale, atol=DEC_ATOL, rtol=0)
 
 
 @pytest.mark.gpu

@@ -9,7 +9,7 @@ backend_renderer.py:24-31).  The "hwc" layout stores each pixel's 192 weights
 contiguously and returns the (192, H, W) view with strides (1, 192 W, 192):
 the same values (bit-exact against the oracle and against the reference
 layout), and those .view calls and the einsum run on it unchanged.  The decode
-(csrc/quick.hip, k_quick_decode_l<., ., HWC>) reads it in 32-B pieces; its
+(csrc/quick_decode.hip, k_quick_decode_l<., ., HWC>) reads it in 32-B pieces; its
 arithmetic is the same, so its output equals the reference-layout decode bit
 for bit."""
 import numpy as np
