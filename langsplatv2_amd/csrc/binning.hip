@@ -134,7 +134,7 @@ hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t* part, si
 
 // Publish the scan total: writes it as the closing entry of the tile-start
 // array (tile_end, may be null) and, packed with a sequence number, into a
-// coherent pinned host word the host spins on (lsr_api.hip wait_published):
+// coherent pinned host word the host spins on (lsr_api.hip bin_tiles, wait_published):
 // the host needs M to size the binning workspace, and polling one
 // PCIe-visible word avoids the staged D2H copy + stream-synchronise wake-up
 // latency in the middle of every forward.  Totals >= 2^32 - 1 saturate (the

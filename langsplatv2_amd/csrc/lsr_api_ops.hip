@@ -1,0 +1,288 @@
+// lsr_api_ops.hip — the C ABI's stateless entry points: each validates its
+// arguments, requests a workspace where it needs one and enqueues one kernel
+// family on the caller's stream.  The codes, and which of two failing checks
+// wins, are behaviour: tools/asan_host_check.py holds the table.
+#include <math.h>
+#include "lsr_api_common.h"
+
+using namespace lsr;
+
+namespace {
+
+// the decode / query kernels' codebooks: L levels of K = 64 codes, Df a multiple of 16
+int codebook_args(int L, int K, int Df)
+{
+    if (L < 0 || Df <= 0 || (Df % 16) != 0) return LSR_EINVAL;
+    return K == 64 ? LSR_OK : LSR_EUNSUPPORTED;
+}
+
+bool layout_ok(int layout) { return layout == LSR_LAYOUT_CHW || layout == LSR_LAYOUT_HWC; }
+
+bool misaligned16(const void* p) { return ((uintptr_t)p % 16) != 0; }
+
+int lang_loss_args(const float* wm, const float* cb, int K, int Df, int H, int W, const int32_t* seg,
+                   const float* feat, int S)
+{
+    if (K <= 0 || Df <= 0 || H <= 0 || W <= 0 || S < 0) return LSR_EINVAL;
+    if (K != 64 || (Df % 16) != 0) return LSR_EUNSUPPORTED;
+    if (!wm || !cb || !seg || (S > 0 && !feat)) return LSR_EINVAL;
+    return LSR_OK;
+}
+
+// a code count the kernels are not built for is unsupported, anything else invalid
+int topk_code_args(int64_t N, int L, int K, int k)
+{
+    if (N >= 0 && L >= 1 && K >= 64 && K <= 256 && (K % 64) == 0 && k >= 1 && k <= K &&
+        N <= (int64_t)0x7fffffff / ((int64_t)L * K))
+        return LSR_OK;
+    return (K % 64 || K > 256) && K > 0 ? LSR_EUNSUPPORTED : LSR_EINVAL;
+}
+
+// dense: g is dL/d(dense codes); sparse: dL/dweights of the packed (N, L*k) form
+int topk_code_backward(const float* logits, const float* g, int64_t N, int L, int K, int k, float* grad_logits,
+                       void* stream, bool sparse)
+{
+    LSR_TRY(topk_code_args(N, L, K, k));
+    if (N == 0) return LSR_OK;
+    if (!logits || !g || !grad_logits) return LSR_EINVAL;
+    LSR_HIP(launch_topk_code_bwd(logits, g, N, L, K, k, grad_logits, (hipStream_t)stream, sparse));
+    return LSR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsr_quick_decode(const float* weight_map, const float* codebooks, int L, int K, int Df, int H, int W,
+                     int normalize, float eps, float* out, lsr_alloc_fn alloc, void* alloc_ctx, void* stream)
+{
+    if (H < 0 || W < 0) return LSR_EINVAL;
+    LSR_TRY(codebook_args(L, K, Df));
+    if (L == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!weight_map || !codebooks || !out) return LSR_EINVAL;
+    void* ws = nullptr;
+    const size_t wsb = quick_decode_workspace_bytes(L, K, Df, normalize);
+    if (wsb) {
+        if (!alloc) return LSR_EINVAL;
+        ws = alloc(alloc_ctx, wsb, LSR_BUF_DECODE);
+        if (!ws) return LSR_ENOMEM;
+    }
+    LSR_HIP(launch_quick_decode(weight_map, codebooks, L, K, Df, H, W, normalize, eps, ws, out, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_quick_pack_codes(const void* indices, int index_dtype, int64_t N, int K, int quick_dim, uint32_t* packed,
+                         void* stream)
+{
+    if (N < 0 || quick_dim < 0 || index_dtype < LSR_INDEX_F32 || index_dtype > LSR_INDEX_I64) return LSR_EINVAL;
+    if (K != 12 || quick_dim > 255) return LSR_EUNSUPPORTED;
+    if (N == 0) return LSR_OK;
+    if (!indices || !packed || misaligned16(packed)) return LSR_EINVAL;
+    LSR_HIP(launch_quick_pack_codes(indices, index_dtype, N, quick_dim > 0 ? quick_dim : 192, packed,
+                                    (hipStream_t)stream));
+    return LSR_OK;
+}
+
+size_t lsr_quick_decode_plan_bytes(int L, int K, int Df, int normalize)
+{
+    if (codebook_args(L, K, Df) != LSR_OK) return 0;
+    return quick_decode_workspace_bytes(L, K, Df, normalize);
+}
+
+int lsr_quick_decode_prepare(const float* codebooks, int L, int K, int Df, int normalize, void* plan, void* stream)
+{
+    LSR_TRY(codebook_args(L, K, Df));
+    if (L == 0) return LSR_OK;
+    if (!codebooks || !plan) return LSR_EINVAL;
+    LSR_HIP(launch_quick_decode_prepare(codebooks, L, K, Df, normalize, plan, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_quick_decode_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int Df, int H,
+                         int W, int normalize, float eps, float* out, void* stream)
+{
+    if (H < 0 || W < 0 || !layout_ok(weight_layout)) return LSR_EINVAL;
+    LSR_TRY(codebook_args(L, K, Df));
+    if (L == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!weight_map || !plan || !out) return LSR_EINVAL;
+    const bool hwc = weight_layout == LSR_LAYOUT_HWC;
+    // the pixel-major map is read in 32-B pieces by the level-resident kernel (Df <= 512)
+    if (hwc && (Df > 512 || misaligned16(weight_map))) return LSR_EUNSUPPORTED;
+    LSR_HIP(launch_quick_decode_run(weight_map, L, K, Df, H, W, normalize, eps, plan, out, (hipStream_t)stream, hwc));
+    return LSR_OK;
+}
+
+size_t lsr_quick_query_plan_bytes(int L, int K, int Df, int n_pos, int n_neg)
+{
+    if (codebook_args(L, K, Df) != LSR_OK || n_pos < 1 || n_neg < 0 || n_pos + n_neg > 64) return 0;
+    return quick_query_plan_bytes(L, K, n_pos, n_neg);
+}
+
+int lsr_quick_query_prepare(const float* codebooks, const float* pos, const float* neg, int L, int K, int Df,
+                            int n_pos, int n_neg, void* plan, void* stream)
+{
+    if (n_pos < 1 || n_neg < 0) return LSR_EINVAL;
+    LSR_TRY(codebook_args(L, K, Df));
+    if (n_pos + n_neg > 64) return LSR_EUNSUPPORTED;
+    if (L == 0) return LSR_OK;
+    if (!codebooks || !pos || (n_neg > 0 && !neg) || !plan) return LSR_EINVAL;
+    LSR_HIP(launch_quick_query_prepare(codebooks, pos, neg, L, K, Df, n_pos, n_neg, plan, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_quick_query_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int n_pos,
+                        int n_neg, int H, int W, int mode, float scale, float eps, float* out, void* stream)
+{
+    if (L < 0 || H < 0 || W < 0 || n_pos < 1 || n_neg < 0 || !layout_ok(weight_layout)) return LSR_EINVAL;
+    if (mode != LSR_QUERY_RELEVANCY && mode != LSR_QUERY_COSINE) return LSR_EINVAL;
+    const bool relevancy = mode == LSR_QUERY_RELEVANCY;
+    // min_j softmax = sigmoid(scale (sim_pos - max_j sim_neg_j)) needs scale >= 0
+    if (relevancy && !(scale >= 0.f)) return LSR_EINVAL;
+    if (K != 64 || n_pos + n_neg > 64 || (relevancy && n_neg < 1)) return LSR_EUNSUPPORTED;
+    if (L == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!weight_map || !plan || !out) return LSR_EINVAL;
+    const bool hwc = weight_layout == LSR_LAYOUT_HWC;
+    // the pixel-major map is read in 16-B pieces
+    if (hwc && misaligned16(weight_map)) return LSR_EUNSUPPORTED;
+    LSR_HIP(launch_quick_query_run(weight_map, hwc, plan, L, K, n_pos, n_neg, H, W, relevancy, scale, eps, out,
+                                   (hipStream_t)stream));
+    return LSR_OK;
+}
+
+size_t lsr_query_post_workspace_bytes(int planes, int H, int W)
+{
+    return query_post_workspace_bytes(planes, H, W);
+}
+
+int lsr_query_smooth(const float* rel, int planes, int H, int W, int kernel, float* avg, float* blend, float* stats,
+                     int64_t* loc, void* workspace, void* stream)
+{
+    if (planes < 0 || H < 0 || W < 0 || kernel < 1 || (kernel & 1) == 0) return LSR_EINVAL;
+    if (kernel > 63 || !query_post_shape_ok(planes, H, W)) return LSR_EUNSUPPORTED;
+    if (planes == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!rel || !stats || !loc || !workspace) return LSR_EINVAL;
+    LSR_HIP(launch_query_smooth(rel, planes, H, W, (kernel - 1) / 2, avg, blend, stats, loc, workspace,
+                                (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_query_mask(const float* blend, const float* stats, const uint8_t* gt_masks, int planes, int n_prompt, int H,
+                   int W, float thresh, int smooth_kernel, uint8_t* mask, int64_t* counts, float* masked_sum,
+                   void* workspace, void* stream)
+{
+    if (planes < 0 || H < 0 || W < 0 || smooth_kernel < 1 || (smooth_kernel & 1) == 0) return LSR_EINVAL;
+    if (gt_masks && (n_prompt < 1 || planes % n_prompt != 0)) return LSR_EINVAL;
+    if (smooth_kernel > 15 || !query_post_shape_ok(planes, H, W)) return LSR_EUNSUPPORTED;
+    if (planes == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!blend || !stats || !mask || !counts || !masked_sum || !workspace) return LSR_EINVAL;
+    LSR_HIP(launch_query_mask(blend, stats, gt_masks, planes, n_prompt, H, W, thresh, (smooth_kernel - 1) / 2, mask,
+                              counts, masked_sum, workspace, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_lang_loss_forward(const float* weight_map, const float* codebooks, int K, int Df, int H, int W,
+                          const int32_t* seg, const float* features, int S, float* loss, float* pixel_stats,
+                          lsr_alloc_fn alloc, void* alloc_ctx, void* stream)
+{
+    LSR_TRY(lang_loss_args(weight_map, codebooks, K, Df, H, W, seg, features, S));
+    if ((!loss && !pixel_stats) || !alloc) return LSR_EINVAL;
+    float* ws = (float*)alloc(alloc_ctx, lang_loss_workspace_bytes(S, W, H, nullptr), LSR_BUF_LOSS);
+    if (!ws) return LSR_ENOMEM;
+    LSR_HIP(launch_lang_loss(weight_map, codebooks, Df, H, W, seg, features, S, nullptr, loss, nullptr, nullptr,
+                             pixel_stats, ws, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_lang_loss_backward(const float* weight_map, const float* codebooks, int K, int Df, int H, int W,
+                           const int32_t* seg, const float* features, int S, const float* pixel_stats,
+                           const float* grad_loss, float* grad_weight_map, float* grad_codebooks, lsr_alloc_fn alloc,
+                           void* alloc_ctx, void* stream)
+{
+    LSR_TRY(lang_loss_args(weight_map, codebooks, K, Df, H, W, seg, features, S));
+    if (!grad_loss || !grad_weight_map || !grad_codebooks || !alloc) return LSR_EINVAL;
+    float* ws = (float*)alloc(alloc_ctx, lang_loss_workspace_bytes(S, W, H, nullptr), LSR_BUF_LOSS);
+    if (!ws) return LSR_ENOMEM;
+    LSR_HIP(launch_lang_loss(weight_map, codebooks, Df, H, W, seg, features, S, grad_loss, nullptr, grad_weight_map,
+                             grad_codebooks, const_cast<float*>(pixel_stats), ws, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double lr,
+                  double beta1, double beta2, double eps, double weight_decay, int64_t step, void* stream)
+{
+    if (n < 0 || step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return LSR_EINVAL;
+    if (n == 0) return LSR_OK;
+    if (!params || !grads || !exp_avg || !exp_avg_sq) return LSR_EINVAL;
+    // scalars as torch forms them: Python doubles, rounded once to fp32
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    AdamArgs a;
+    a.one_minus_b1 = (float)(1.0 - beta1);
+    a.b2 = (float)beta2;
+    a.one_minus_b2 = (float)(1.0 - beta2);
+    a.eps = (float)eps;
+    a.step_size = (float)(lr / bc1);
+    a.bc2_sqrt = (float)sqrt(bc2);
+    a.weight_decay = (float)weight_decay;
+    LSR_HIP(launch_adam(params, grads, exp_avg, exp_avg_sq, n, a, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_topk_code_forward(const float* logits, int64_t N, int L, int K, int k, float* dense, float* sparse_w,
+                          void* sparse_idx, int idx_dtype, int level_offset, void* stream)
+{
+    LSR_TRY(topk_code_args(N, L, K, k));
+    if (idx_dtype < LSR_INDEX_F32 || idx_dtype > LSR_INDEX_I64) return LSR_EINVAL;
+    if (N == 0) return LSR_OK;
+    if (!logits || (!dense && !sparse_w && !sparse_idx)) return LSR_EINVAL;
+    LSR_HIP(launch_topk_code_fwd(logits, N, L, K, k, dense, sparse_w, sparse_idx, idx_dtype, level_offset,
+                                 (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_topk_code_backward(const float* logits, const float* grad_dense, int64_t N, int L, int K, int k,
+                           float* grad_logits, void* stream)
+{
+    return topk_code_backward(logits, grad_dense, N, L, K, k, grad_logits, stream, false);
+}
+
+int lsr_topk_code_backward_sparse(const float* logits, const float* grad_weights, int64_t N, int L, int K, int k,
+                                  float* grad_logits, void* stream)
+{
+    return topk_code_backward(logits, grad_weights, N, L, K, k, grad_logits, stream, true);
+}
+
+int lsr_knn_dist2(const float* points, int64_t N, float* out, lsr_alloc_fn alloc, void* alloc_ctx, void* stream)
+{
+    if (N < 0 || N > 0x7fffffffLL) return LSR_EINVAL;
+    if (N == 0) return LSR_OK;
+    if (!points || !out || !alloc) return LSR_EINVAL;
+    size_t sort_temp = 0;
+    LSR_HIP(knn_sort_temp_bytes(N, &sort_temp));
+    uint8_t* ws = (uint8_t*)alloc(alloc_ctx, knn_workspace_bytes(N, sort_temp), LSR_BUF_KNN);
+    if (!ws) return LSR_ENOMEM;
+    LSR_HIP(launch_knn_dist2(points, N, out, ws, sort_temp, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_sh_grad_from_views(int64_t N, int M, int sh_degree, const float* means3D, int R, const float* campos,
+                           const float* drgb, float* dL_dsh, void* stream)
+{
+    if (N < 0 || M < 1 || M > 16 || sh_degree < 0 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > M || R < 0)
+        return LSR_EINVAL;
+    if (N == 0) return LSR_OK;
+    if (!means3D || !dL_dsh || (R > 0 && (!campos || !drgb))) return LSR_EINVAL;
+    LSR_HIP(launch_sh_grad_from_views(N, M, sh_degree, means3D, R, campos, drgb, dL_dsh, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
+                     void* stream)
+{
+    (void)projmatrix;
+    if (P < 0 || (P > 0 && (!means3D || !viewmatrix || !present))) return LSR_EINVAL;
+    LSR_HIP(launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+}  // extern "C"

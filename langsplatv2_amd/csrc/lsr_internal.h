@@ -1,5 +1,8 @@
 // lsr_internal.h — launcher declarations shared by the kernel translation
-// units and the C-ABI driver (lsr_api.hip).  Not part of the public ABI.
+// units and the C-ABI driver (lsr_api.hip: forward and backward; lsr_api_ops.hip:
+// the single-kernel entry points; lsr_api_runtime.hip: options, profiling,
+// streams; their shared macros, profiler and guard: lsr_api_common.h).  Not part
+// of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

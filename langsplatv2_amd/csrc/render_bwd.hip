@@ -337,7 +337,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bwd_wav
     static_assert(!LD || (!LO && NL % 16 == 0), "direct dL/dlang needs whole 16-channel lines");
     using FR = BwdFrags<NL>;
     constexpr int KS = FR::KS;
-    // LD implies D == NL (launch_render_bwd) and 16-B aligned rows (lsr_api)
+    // LD implies D == NL (launch_render_bwd) and 16-B aligned rows (lsr_api.hip plan_backward)
     constexpr bool VEC = LD;
     // RREG (direct dL/dlang): the language lines' atomics take their values
     // straight from the MFMA accumulators, lane (li, lg) adding candidate

@@ -3,7 +3,7 @@
 With a gradient pending, the forward allocates the gradient rows (and the
 (N, D) dL/dlang accumulator) and zeroes them inside the render kernel; the
 backward adds into them instead of clearing its own with two memsets
-(lsr_api.hip grad_ws_layout, render_fwd.hip zero_backward_accumulators).  A
+(lsr_api.hip plan_backward, render_fwd.hip zero_backward_accumulators).  A
 second backward over the same graph (retain_graph) finds the workspace taken
 and clears its own, so the two must agree: they sum the same per-pair terms,
 in an arrival order the atomics do not fix (harness.GRAD_RTOL).

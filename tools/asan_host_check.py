@@ -94,6 +94,217 @@ assert lib.lsr_quick_decode_run(None, 2, None, 3, 64, 16, 4, 4, 1, 1e-10, None, 
 assert lib.lsr_knn_dist2(None, -5, None, ALLOC, None, None) == EINVAL
 assert lib.lsr_adam_step(None, None, None, None, -1, 0.1, 0.9, 0.999, 1e-8, 0.0, 1, None) == EINVAL
 calls += 9
+# The return-code table of the single-kernel entry points: (function, arguments,
+# expected code), every call rejected -- or a no-op -- before any HIP call.  The
+# codes, and which of two failing checks wins ("both"), are part of the ABI's
+# behaviour; tests/test_api_codes.py runs this table against the regular build.
+OK, ENOMEM = 0, 4
+NOALLOC = L.ALLOC_FN()   # a NULL allocator
+ODD = P + 4              # a pointer that is not 16-B aligned
+NAN = float("nan")
+TABLE = [
+    # lsr_quick_decode(wmap, cb, L, K, Df, H, W, normalize, eps, out, alloc, ctx, stream)
+    ("lsr_quick_decode", (None, None, 3, 32, 500, 4, 4, 1, 1e-10, None, ALLOC, None, None), EINVAL),   # both
+    ("lsr_quick_decode", (None, None, 3, 64, 0, 4, 4, 1, 1e-10, None, ALLOC, None, None), EINVAL),
+    ("lsr_quick_decode", (None, None, 0, 64, 512, 4, 4, 1, 1e-10, None, ALLOC, None, None), OK),
+    ("lsr_quick_decode", (None, None, 3, 64, 512, 4, 4, 1, 1e-10, None, ALLOC, None, None), EINVAL),
+    ("lsr_quick_decode", (P, P, 3, 64, 512, 4, 4, 1, 1e-10, P, NOALLOC, None, None), EINVAL),
+    ("lsr_quick_decode", (P, P, 3, 64, 512, 4, 4, 1, 1e-10, P, ALLOC, None, None), ENOMEM),
+    # lsr_quick_decode_prepare(cb, L, K, Df, normalize, plan, stream)
+    ("lsr_quick_decode_prepare", (None, 3, 32, 512, 1, None, None), EUNSUP),
+    ("lsr_quick_decode_prepare", (None, 3, 32, 8, 1, None, None), EINVAL),   # both
+    ("lsr_quick_decode_prepare", (None, 0, 64, 512, 1, None, None), OK),
+    ("lsr_quick_decode_prepare", (P, 3, 64, 512, 1, None, None), EINVAL),
+    # lsr_quick_decode_run(wmap, layout, plan, L, K, Df, H, W, normalize, eps, out, stream)
+    ("lsr_quick_decode_run", (None, 0, None, 3, 32, 512, 4, 4, 1, 1e-10, None, None), EUNSUP),
+    ("lsr_quick_decode_run", (None, 2, None, 3, 32, 512, 4, 4, 1, 1e-10, None, None), EINVAL),   # both
+    ("lsr_quick_decode_run", (None, 0, None, 3, 32, 17, 4, 4, 1, 1e-10, None, None), EINVAL),    # both
+    ("lsr_quick_decode_run", (None, 1, None, 0, 64, 512, 4, 4, 1, 1e-10, None, None), OK),
+    ("lsr_quick_decode_run", (None, 0, None, 3, 64, 512, 0, 4, 1, 1e-10, None, None), OK),
+    ("lsr_quick_decode_run", (None, 0, None, 3, 64, 512, 4, 4, 1, 1e-10, None, None), EINVAL),
+    ("lsr_quick_decode_run", (P, 1, P, 3, 64, 1024, 4, 4, 1, 1e-10, P, None), EUNSUP),
+    ("lsr_quick_decode_run", (ODD, 1, P, 3, 64, 512, 4, 4, 1, 1e-10, P, None), EUNSUP),
+    ("lsr_quick_decode_run", (ODD, 1, P, 3, 64, 512, 4, -1, 1, 1e-10, P, None), EINVAL),
+    # lsr_quick_pack_codes(indices, dtype, N, K, quick_dim, packed, stream)
+    ("lsr_quick_pack_codes", (None, 0, -1, 12, 192, None, None), EINVAL),
+    ("lsr_quick_pack_codes", (None, 3, 10, 12, 192, None, None), EINVAL),
+    ("lsr_quick_pack_codes", (None, 3, 10, 8, 192, None, None), EINVAL),    # both
+    ("lsr_quick_pack_codes", (None, 0, 10, 12, -1, None, None), EINVAL),
+    ("lsr_quick_pack_codes", (None, 0, 10, 8, 192, None, None), EUNSUP),
+    ("lsr_quick_pack_codes", (None, 1, 10, 12, 256, None, None), EUNSUP),
+    ("lsr_quick_pack_codes", (None, 2, 0, 12, 0, None, None), OK),
+    ("lsr_quick_pack_codes", (None, 2, 0, 13, 0, None, None), EUNSUP),      # K before the no-op
+    ("lsr_quick_pack_codes", (None, 0, 10, 12, 192, P, None), EINVAL),
+    ("lsr_quick_pack_codes", (P, 0, 10, 12, 192, ODD, None), EINVAL),
+    # lsr_quick_query_prepare(cb, pos, neg, L, K, Df, n_pos, n_neg, plan, stream)
+    ("lsr_quick_query_prepare", (None, None, None, 3, 64, 17, 1, 1, None, None), EINVAL),
+    ("lsr_quick_query_prepare", (None, None, None, 3, 64, 512, 0, 1, None, None), EINVAL),
+    ("lsr_quick_query_prepare", (None, None, None, -1, 64, 512, 1, 1, None, None), EINVAL),
+    ("lsr_quick_query_prepare", (None, None, None, 3, 32, 512, 1, 1, None, None), EUNSUP),
+    ("lsr_quick_query_prepare", (None, None, None, 3, 64, 512, 33, 32, None, None), EUNSUP),
+    ("lsr_quick_query_prepare", (None, None, None, 3, 32, 17, 1, 1, None, None), EINVAL),   # both
+    ("lsr_quick_query_prepare", (None, None, None, 0, 64, 512, 1, 1, None, None), OK),
+    ("lsr_quick_query_prepare", (None, None, None, 3, 64, 512, 1, 1, None, None), EINVAL),
+    ("lsr_quick_query_prepare", (P, P, None, 3, 64, 512, 1, 1, P, None), EINVAL),
+    # lsr_quick_query_run(wmap, layout, plan, L, K, n_pos, n_neg, H, W, mode, scale, eps, out, stream)
+    ("lsr_quick_query_run", (None, 2, None, 3, 64, 1, 1, 4, 4, 0, 10.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_query_run", (None, 0, None, 3, 64, 1, 1, 4, 4, 2, 10.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_query_run", (None, 0, None, 3, 64, 1, 1, 4, 4, 0, -1.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_query_run", (None, 0, None, 3, 64, 1, 1, 4, 4, 0, NAN, 1e-10, None, None), EINVAL),
+    ("lsr_quick_query_run", (None, 0, None, 3, 64, 0, 1, 4, 4, 0, 10.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_query_run", (None, 0, None, 3, 32, 1, 1, 4, 4, 0, 10.0, 1e-10, None, None), EUNSUP),
+    ("lsr_quick_query_run", (None, 0, None, 3, 64, 1, 0, 4, 4, 0, 10.0, 1e-10, None, None), EUNSUP),
+    ("lsr_quick_query_run", (None, 0, None, 3, 64, 40, 30, 4, 4, 1, 10.0, 1e-10, None, None), EUNSUP),
+    ("lsr_quick_query_run", (None, 5, None, 3, 32, 1, 1, 4, 4, 0, 10.0, 1e-10, None, None), EINVAL),   # both
+    ("lsr_quick_query_run", (None, 0, None, 3, 32, 1, 0, 4, 4, 0, -1.0, 1e-10, None, None), EINVAL),   # both
+    ("lsr_quick_query_run", (None, 0, None, 3, 64, 1, 0, 0, 4, 0, 10.0, 1e-10, None, None), EUNSUP),   # before the no-op
+    ("lsr_quick_query_run", (None, 0, None, 3, 64, 1, 1, 0, 4, 0, 10.0, 1e-10, None, None), OK),
+    ("lsr_quick_query_run", (None, 1, None, 0, 64, 1, 0, 4, 4, 1, -1.0, 1e-10, None, None), OK),
+    ("lsr_quick_query_run", (None, 0, None, 3, 64, 1, 1, 4, 4, 0, 10.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_query_run", (ODD, 1, P, 3, 64, 1, 1, 4, 4, 0, 10.0, 1e-10, P, None), EUNSUP),
+    # lsr_query_smooth(rel, planes, H, W, kernel, avg, blend, stats, loc, workspace, stream)
+    ("lsr_query_smooth", (None, 2, 4, 4, 4, None, None, None, None, None, None), EINVAL),
+    ("lsr_query_smooth", (None, 2, 4, 4, 0, None, None, None, None, None, None), EINVAL),
+    ("lsr_query_smooth", (None, -1, 4, 4, 3, None, None, None, None, None, None), EINVAL),
+    ("lsr_query_smooth", (None, 2, 4, 4, 65, None, None, None, None, None, None), EUNSUP),
+    ("lsr_query_smooth", (None, 65536, 4, 4, 3, None, None, None, None, None, None), EUNSUP),
+    ("lsr_query_smooth", (None, 2, 65536, 65536, 3, None, None, None, None, None, None), EUNSUP),
+    ("lsr_query_smooth", (None, 2, 4, 4, 66, None, None, None, None, None, None), EINVAL),   # both
+    ("lsr_query_smooth", (None, 0, 4, 4, 65, None, None, None, None, None, None), EUNSUP),   # before the no-op
+    ("lsr_query_smooth", (None, 0, 4, 4, 3, None, None, None, None, None, None), OK),
+    ("lsr_query_smooth", (None, 2, 4, 0, 63, None, None, None, None, None, None), OK),
+    ("lsr_query_smooth", (None, 2, 4, 4, 3, None, None, None, None, None, None), EINVAL),
+    ("lsr_query_smooth", (P, 2, 4, 4, 3, None, None, P, P, None, None), EINVAL),
+    # lsr_query_mask(blend, stats, gt, planes, n_prompt, H, W, thresh, smooth_kernel, mask, counts, masked_sum,
+    #                workspace, stream)
+    ("lsr_query_mask", (None, None, None, 2, 1, 4, 4, 0.5, 2, None, None, None, None, None), EINVAL),
+    ("lsr_query_mask", (None, None, P, 2, 0, 4, 4, 0.5, 3, None, None, None, None, None), EINVAL),
+    ("lsr_query_mask", (None, None, P, 3, 2, 4, 4, 0.5, 3, None, None, None, None, None), EINVAL),
+    ("lsr_query_mask", (None, None, None, 2, 1, 4, 4, 0.5, 17, None, None, None, None, None), EUNSUP),
+    ("lsr_query_mask", (None, None, None, 70000, 1, 4, 4, 0.5, 3, None, None, None, None, None), EUNSUP),
+    ("lsr_query_mask", (None, None, P, 2, 0, 4, 4, 0.5, 17, None, None, None, None, None), EINVAL),   # both
+    ("lsr_query_mask", (None, None, None, 2, 1, 4, 4, 0.5, 18, None, None, None, None, None), EINVAL),   # both
+    ("lsr_query_mask", (None, None, None, 2, 0, 4, 0, 0.5, 3, None, None, None, None, None), OK),
+    ("lsr_query_mask", (None, None, None, 0, 1, 4, 4, 0.5, 15, None, None, None, None, None), OK),
+    ("lsr_query_mask", (None, None, None, 2, 1, 4, 4, 0.5, 3, None, None, None, None, None), EINVAL),
+    ("lsr_query_mask", (P, P, None, 2, 1, 4, 4, 0.5, 3, P, P, P, None, None), EINVAL),
+    # lsr_lang_loss_forward(wmap, cb, K, Df, H, W, seg, feat, S, loss, pixel_stats, alloc, ctx, stream):
+    # an empty image is an error here, not a no-op
+    ("lsr_lang_loss_forward", (P, P, 0, 512, 4, 4, P, P, 2, P, None, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_forward", (P, P, 64, 512, 0, 4, P, P, 2, P, None, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_forward", (P, P, 32, 512, 4, 4, P, P, 2, P, None, ALLOC, None, None), EUNSUP),
+    ("lsr_lang_loss_forward", (P, P, 64, 24, 4, 4, P, P, 2, P, None, ALLOC, None, None), EUNSUP),
+    ("lsr_lang_loss_forward", (P, P, 32, 512, 4, 4, P, P, -1, P, None, ALLOC, None, None), EINVAL),   # both
+    ("lsr_lang_loss_forward", (None, P, 32, 512, 4, 4, P, P, 2, P, None, ALLOC, None, None), EUNSUP),  # both
+    ("lsr_lang_loss_forward", (None, P, 64, 512, 4, 4, P, P, 2, P, None, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_forward", (P, P, 64, 512, 4, 4, P, None, 2, P, None, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_forward", (P, P, 64, 512, 4, 4, P, None, 0, None, None, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_forward", (P, P, 64, 512, 4, 4, P, P, 2, P, None, NOALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_forward", (P, P, 64, 512, 4, 4, P, None, 0, None, P, ALLOC, None, None), ENOMEM),
+    # lsr_lang_loss_backward(wmap, cb, K, Df, H, W, seg, feat, S, pixel_stats, grad_loss, grad_wmap, grad_cb,
+    #                        alloc, ctx, stream)
+    ("lsr_lang_loss_backward", (P, P, 64, 0, 4, 4, P, P, 2, None, P, P, P, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_backward", (P, P, 64, 512, 4, -4, P, P, 2, None, P, P, P, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_backward", (P, P, 128, 512, 4, 4, P, P, 2, None, P, P, P, ALLOC, None, None), EUNSUP),
+    ("lsr_lang_loss_backward", (P, P, 128, 520, 0, 4, P, P, 2, None, P, P, P, ALLOC, None, None), EINVAL),   # both
+    ("lsr_lang_loss_backward", (P, P, 64, 520, 4, 4, P, P, 2, None, None, P, P, ALLOC, None, None), EUNSUP),  # both
+    ("lsr_lang_loss_backward", (P, P, 64, 512, 4, 4, None, P, 2, None, P, P, P, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_backward", (P, P, 64, 512, 4, 4, P, P, 2, None, None, P, P, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_backward", (P, P, 64, 512, 4, 4, P, P, 2, None, P, P, None, ALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_backward", (P, P, 64, 512, 4, 4, P, P, 2, None, P, P, P, NOALLOC, None, None), EINVAL),
+    ("lsr_lang_loss_backward", (P, P, 64, 512, 4, 4, P, P, 2, P, P, P, P, ALLOC, None, None), ENOMEM),
+    # lsr_topk_code_forward(logits, N, L, K, k, dense, sparse_w, sparse_idx, idx_dtype, level_offset, stream)
+    ("lsr_topk_code_forward", (None, 10, 1, 320, 4, None, None, None, 0, 0, None), EUNSUP),
+    ("lsr_topk_code_forward", (None, 10, 1, 48, 0, None, None, None, 7, 0, None), EUNSUP),   # both
+    ("lsr_topk_code_forward", (None, 10, 1, 0, 4, None, None, None, 0, 0, None), EINVAL),
+    ("lsr_topk_code_forward", (None, 10, 1, -64, 4, None, None, None, 0, 0, None), EINVAL),
+    ("lsr_topk_code_forward", (None, 10, 1, 64, 4, None, None, None, 3, 0, None), EINVAL),
+    ("lsr_topk_code_forward", (None, 0, 1, 64, 4, None, None, None, -1, 0, None), EINVAL),   # dtype before the no-op
+    # lsr_topk_code_backward(logits, grad_dense, N, L, K, k, grad_logits, stream)
+    ("lsr_topk_code_backward", (None, None, 10, 1, 100, 4, None, None), EUNSUP),
+    ("lsr_topk_code_backward", (None, None, 10, 0, 64, 4, None, None), EINVAL),
+    ("lsr_topk_code_backward", (None, None, 0, 3, 128, 4, None, None), OK),
+    ("lsr_topk_code_backward", (P, P, 10, 3, 128, 4, None, None), EINVAL),
+    # lsr_topk_code_backward_sparse(logits, grad_weights, N, L, K, k, grad_logits, stream)
+    ("lsr_topk_code_backward_sparse", (None, None, 10, 1, 48, 4, None, None), EUNSUP),
+    ("lsr_topk_code_backward_sparse", (None, None, 10, 1, 320, 4, None, None), EUNSUP),
+    ("lsr_topk_code_backward_sparse", (None, None, 10, 1, 64, 0, None, None), EINVAL),
+    ("lsr_topk_code_backward_sparse", (None, None, 10, 1, 64, 65, None, None), EINVAL),
+    ("lsr_topk_code_backward_sparse", (None, None, -1, 1, 64, 4, None, None), EINVAL),
+    ("lsr_topk_code_backward_sparse", (None, None, 10, 0, 64, 4, None, None), EINVAL),
+    ("lsr_topk_code_backward_sparse", (None, None, 10, 1, 0, 4, None, None), EINVAL),
+    ("lsr_topk_code_backward_sparse", (None, None, 1 << 30, 1, 64, 4, None, None), EINVAL),   # N L K past 2^31
+    ("lsr_topk_code_backward_sparse", (None, None, 10, 1, 48, 0, None, None), EUNSUP),        # both
+    ("lsr_topk_code_backward_sparse", (None, None, -1, 0, 320, 4, None, None), EUNSUP),       # both
+    ("lsr_topk_code_backward_sparse", (None, None, 0, 1, 48, 4, None, None), EUNSUP),         # before the no-op
+    ("lsr_topk_code_backward_sparse", (None, None, 0, 2, 256, 256, None, None), OK),
+    ("lsr_topk_code_backward_sparse", (None, None, 10, 1, 64, 4, None, None), EINVAL),
+    ("lsr_topk_code_backward_sparse", (P, P, 10, 1, 64, 4, None, None), EINVAL),
+    # lsr_sh_grad_from_views(N, M, sh_degree, means3D, R, campos, drgb, dL_dsh, stream): no shape is
+    # "unsupported" here, more than 16 coefficients are an invalid argument
+    ("lsr_sh_grad_from_views", (-1, 16, 3, None, 1, None, None, None, None), EINVAL),
+    ("lsr_sh_grad_from_views", (10, 0, 0, None, 1, None, None, None, None), EINVAL),
+    ("lsr_sh_grad_from_views", (10, 17, 3, None, 1, None, None, None, None), EINVAL),
+    ("lsr_sh_grad_from_views", (10, 25, 4, None, 1, None, None, None, None), EINVAL),
+    ("lsr_sh_grad_from_views", (10, 16, 4, None, 1, None, None, None, None), EINVAL),
+    ("lsr_sh_grad_from_views", (10, 9, 3, None, 1, None, None, None, None), EINVAL),
+    ("lsr_sh_grad_from_views", (10, 16, 3, None, -1, None, None, None, None), EINVAL),
+    ("lsr_sh_grad_from_views", (0, 17, 3, None, 1, None, None, None, None), EINVAL),   # before the no-op
+    ("lsr_sh_grad_from_views", (0, 16, 3, None, 1, None, None, None, None), OK),
+    ("lsr_sh_grad_from_views", (10, 16, 3, None, 0, None, None, P, None), EINVAL),
+    ("lsr_sh_grad_from_views", (10, 16, 3, P, 2, None, P, P, None), EINVAL),
+    ("lsr_sh_grad_from_views", (10, 16, 3, P, 2, P, None, P, None), EINVAL),
+    # lsr_knn_dist2(points, N, out, alloc, ctx, stream); lsr_adam_step(p, g, m, v, n, lr, b1, b2, eps, wd, step, stream)
+    ("lsr_knn_dist2", (None, 1 << 31, None, ALLOC, None, None), EINVAL),
+    ("lsr_knn_dist2", (None, 0, None, ALLOC, None, None), OK),
+    ("lsr_knn_dist2", (P, 10, P, NOALLOC, None, None), EINVAL),
+    ("lsr_adam_step", (None, None, None, None, 10, 0.1, 0.9, 0.999, 1e-8, 0.0, 0, None), EINVAL),
+    ("lsr_adam_step", (None, None, None, None, 10, 0.1, 1.0, 0.999, 1e-8, 0.0, 1, None), EINVAL),
+    ("lsr_adam_step", (None, None, None, None, 10, 0.1, 0.9, NAN, 1e-8, 0.0, 1, None), EINVAL),
+    ("lsr_adam_step", (None, None, None, None, 0, 0.1, 0.9, 0.999, 1e-8, 0.0, 1, None), OK),
+    ("lsr_adam_step", (P, P, P, None, 10, 0.1, 0.9, 0.999, 1e-8, 0.0, 1, None), EINVAL),
+    ("lsr_mark_visible", (10, None, P, P, P, None), EINVAL),
+]
+for fn, args, want in TABLE:
+    rc = getattr(lib, fn)(*args)
+    assert rc == want, (fn, args, rc, want)
+    calls += 1
+# the plan sizes: 0 for a shape the kernels do not take
+for args, some in [((3, 64, 512, 1, 1), True), ((3, 64, 512, 64, 0), True), ((3, 32, 512, 1, 1), False),
+                   ((3, 64, 17, 1, 1), False), ((3, 64, 0, 1, 1), False), ((-1, 64, 512, 1, 1), False),
+                   ((3, 64, 512, 0, 1), False), ((3, 64, 512, 1, -1), False), ((3, 64, 512, 33, 32), False)]:
+    assert (lib.lsr_quick_query_plan_bytes(*args) > 0) == some, args
+    calls += 1
+for args, some in [((3, 64, 512, 0), True), ((-1, 64, 512, 1), False), ((3, 64, 24, 1), False), ((3, 128, 512, 1), False)]:
+    assert (lib.lsr_quick_decode_plan_bytes(*args) > 0) == some, args
+    calls += 1
+for args, some in [((2, 4, 4), True), ((0, 4, 4), False), ((2, 0, 4), False), ((-1, 4, 4), False), ((70000, 4, 4), False)]:
+    assert (lib.lsr_query_post_workspace_bytes(*args) > 0) == some, args
+    calls += 1
+# the render driver past validate(): missing outputs, and the empty scene's backward (a no-op)
+for okw, skw, ikw, want in [(dict(out_color=P, out_lang=P, radii=None), {}, {}, EINVAL),
+                            (dict(out_color=P, out_lang=None, radii=P), dict(include_feature=1),
+                             dict(lang_dim=16, language_feature_precomp=P), EINVAL),
+                            (dict(out_color=P, out_lang=P, radii=P), {}, dict(max_coeffs=25), EUNSUP),
+                            (dict(out_color=P, out_lang=P, radii=P), dict(sh_degree=4), dict(max_coeffs=25), EINVAL),
+                            (dict(out_color=P, out_lang=P, radii=P), dict(include_feature=1),
+                             dict(lang_dim=1000, language_feature_precomp=P), EUNSUP),
+                            (dict(out_color=P, out_lang=P, radii=P), dict(quick_render=1, quick_layout=1),
+                             dict(quick_k=4, language_feature_weights_quick=P, language_feature_indices=P), EUNSUP),
+                            (dict(out_color=P, out_lang=P, radii=P), dict(quick_layout=1), {}, EINVAL)]:
+    rc = lib.lsr_forward(ctypes.byref(settings(**skw)), ctypes.byref(inputs(**ikw)), ctypes.byref(L.FwdOut(**okw)),
+                         ALLOC, None, None)
+    assert rc == want, (okw, skw, ikw, rc)
+    calls += 1
+for bkw, ikw, skw, want in [({}, dict(P=0), {}, OK), (dict(radii=None), {}, {}, EINVAL),
+                            (dict(radii=None), dict(P=0), {}, OK),
+                            ({}, dict(lang_dim=16, language_feature_precomp=P), dict(include_feature=1), EINVAL)]:
+    b = dict(geom=P, binning=P, image=P, num_rendered=0, radii=P, dL_dout_color=P, dL_dout_lang=None)
+    b.update(bkw)
+    rc = lib.lsr_backward(ctypes.byref(settings(**skw)), ctypes.byref(inputs(**ikw)), ctypes.byref(L.BwdIn(**b)),
+                          ctypes.byref(L.BwdOut()), ALLOC, None, None)
+    assert rc == want, (bkw, ikw, skw, rc)
+    calls += 1
 # pure host code: stage-name parsing (random strings), profiling tables, versions
 names = ["preprocess", "scan_tiles", "bin_count", "scan_tile_counts", "bin_scatter", "tile_sort", "render_fwd",
          "grad_zero", "render_bwd", "preprocess_bwd", "det_bounds", "det_finish"]
