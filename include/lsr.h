@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_query_post_workspace_bytes, lsr_query_smooth, lsr_query_mask;
+#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_quick_heat_plan_bytes / _prepare / _run, lsr_heat_frame;
+                               12, additive (no bump): lsr_query_post_workspace_bytes, lsr_query_smooth, lsr_query_mask;
                                12, additive (no bump): lsr_quick_query_plan_bytes / _prepare / _run;
                                12 (r06): LSR_OPT_DETERMINISTIC;
                                11 (r05): LSR_INDEX_PACKED, lsr_quick_pack_codes, LSR_OPT_SPLIT_PREPROCESS;
@@ -325,6 +326,53 @@ int lsr_query_smooth(const float* rel, int planes, int H, int W, int kernel, flo
 int lsr_query_mask(const float* blend, const float* stats, const uint8_t* gt_masks, int planes, int n_prompt, int H,
                    int W, float thresh, int smooth_kernel, uint8_t* mask, int64_t* counts, float* masked_sum,
                    void* workspace, void* stream);
+
+/* The viewers' query maps, one (n_pos, H, W) fp32 map per prompt taken from
+ * all levels of a pixel at once — the decoded (L, Df, H, W) map is never
+ * written (backend_renderer.py:193-233, demo_prompt.py:118-150).  With
+ * f_l = F_l / (|F_l| + eps) the normalised decode of level l:
+ *   LSR_HEAT_SUMMED_COSINE   s = sum_l f_l, out[q] = s . pos_q / (|s| + eps)
+ *                            (the render server; negatives are ignored);
+ *   LSR_HEAT_MEAN_RELEVANCY  (sum_l rel_l[q]) / L in level order, rel_l the
+ *                            relevancy of lsr_quick_query_run (the prompt demo;
+ *                            scale >= 0, n_neg >= 1).
+ * An all-zero pixel gives exactly 0 / 0.5.  lsr_quick_heat_prepare writes the
+ * (codebooks, query set) part — the query plan's projections and norm factors
+ * and the f64 Cholesky factor of the stacked (L K) x (L K) Gram matrix, from
+ * which |s| is a sum of squares — into a caller-owned device buffer of
+ * lsr_quick_heat_plan_bytes bytes (0 = unsupported shape), valid until the
+ * codebooks or the embeddings change; it is not a query plan.  K must be 64,
+ * Df a multiple of 16, L <= 3, n_pos >= 1, n_pos + n_neg <= 64; n_pos and
+ * n_neg must be the plan's.
+ *
+ * lsr_heat_frame: colour, blend and pack.  maps (planes, H, W) fp32, stats
+ * (planes, 3) fp32 = {min, max, unused} per plane (the rows lsr_query_smooth
+ * writes; with kernel = 1 and NULL avg / blend they are the maps' exact
+ * minimum and maximum), rgb (3, H, W) fp32 or NULL, lut (256, 3) uint8 ->
+ * out (planes, H, W, 3) uint8, RGB, pixel-major.  Per plane, every operation
+ * in fp32 and rounded on its own:
+ *   gate   max < threshold or (max - min) < min_range: v = 0 on the plane
+ *   LSR_CURVE_UPPER_HALF  t = (x - min) / ((max - min) + 1e-9f), v = clip(t * 2 - 1, 0, 1)
+ *   LSR_CURVE_POWER4      t = (x - min) / ((max - min) + 1e-8f), v = (t * t) * (t * t)
+ *   heat   = lut[(int)(v * 255.f) clamped to 0..255]
+ *   out_c  = heat_c, or with rgb (uint8)(clip(rgb_c * (1.f - alpha) + ((float)heat_c / 255.f) * alpha, 0, 1) * 255.f)
+ * Non-finite inputs give unspecified bytes (the table is still indexed inside
+ * 0..255).  Bit-identical from run to run.
+ *
+ * LSR_EINVAL: a NULL required pointer, an unknown layout, mode or curve, a
+ * negative or NaN scale or alpha, alpha > 1, n_pos < 1; LSR_EUNSUPPORTED: a
+ * shape out of range (K, L > 3, n_pos + n_neg > 64, mean relevancy without
+ * negatives, a misaligned pixel-major map, more than 65535 planes, H * W near
+ * 2^31); L, H, W or planes = 0: LSR_OK with nothing launched.  Additive to ABI 12. */
+enum { LSR_HEAT_SUMMED_COSINE = 0, LSR_HEAT_MEAN_RELEVANCY = 1 };
+enum { LSR_CURVE_UPPER_HALF = 0, LSR_CURVE_POWER4 = 1 };
+size_t lsr_quick_heat_plan_bytes(int L, int K, int Df, int n_pos, int n_neg);
+int lsr_quick_heat_prepare(const float* codebooks, const float* pos, const float* neg, int L, int K, int Df,
+                           int n_pos, int n_neg, void* plan, void* stream);
+int lsr_quick_heat_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int n_pos, int n_neg,
+                       int H, int W, int mode, float scale, float eps, float* out, void* stream);
+int lsr_heat_frame(const float* maps, const float* stats, const float* rgb, const uint8_t* lut, int planes, int H, int W,
+                   int curve, float threshold, float min_range, float alpha, uint8_t* out, void* stream);
 
 /* Fused top-k soft codes (replaces softmax_to_topk_soft_code,
  * utils/vq_utils.py:9-24; get_weights_and_indices, :26-40; the per-level

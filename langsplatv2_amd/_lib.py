@@ -23,6 +23,8 @@ LSR_INDEX_F32, LSR_INDEX_I32, LSR_INDEX_I64, LSR_INDEX_PACKED = 0, 1, 2, 3
 LSR_GWS_GEOM, LSR_GWS_LANG = 1, 2
 LSR_LAYOUT_CHW, LSR_LAYOUT_HWC = 0, 1
 LSR_QUERY_RELEVANCY, LSR_QUERY_COSINE = 0, 1
+LSR_HEAT_SUMMED_COSINE, LSR_HEAT_MEAN_RELEVANCY = 0, 1
+LSR_CURVE_UPPER_HALF, LSR_CURVE_POWER4 = 0, 1
 
 _vp = ctypes.c_void_p
 
@@ -128,7 +130,8 @@ ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c
 
 EXPORTS = ("lsr_forward", "lsr_backward", "lsr_mark_visible", "lsr_quick_decode", "lsr_quick_decode_plan_bytes",
            "lsr_quick_decode_prepare", "lsr_quick_decode_run", "lsr_quick_query_plan_bytes", "lsr_quick_query_prepare",
-           "lsr_quick_query_run", "lsr_query_post_workspace_bytes", "lsr_query_smooth", "lsr_query_mask",
+           "lsr_quick_query_run", "lsr_quick_heat_plan_bytes", "lsr_quick_heat_prepare", "lsr_quick_heat_run",
+           "lsr_heat_frame", "lsr_query_post_workspace_bytes", "lsr_query_smooth", "lsr_query_mask",
            "lsr_quick_pack_codes", "lsr_topk_code_forward",
            "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_adam_step", "lsr_sh_grad_from_views", "lsr_strerror",
            "lsr_abi_version", "lsr_max_lang_dim", "lsr_profile_enable", "lsr_profile_stages", "lsr_profile_reset",
@@ -174,6 +177,15 @@ def load(path: str | None = None):
     lib.lsr_quick_query_run.argtypes = [_vp, ctypes.c_int, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float,
                                                                                       _vp, _vp]
     lib.lsr_quick_query_run.restype = ctypes.c_int
+    lib.lsr_quick_heat_plan_bytes.argtypes = [ctypes.c_int] * 5
+    lib.lsr_quick_heat_plan_bytes.restype = ctypes.c_size_t
+    lib.lsr_quick_heat_prepare.argtypes = [_vp, _vp, _vp] + [ctypes.c_int] * 5 + [_vp, _vp]
+    lib.lsr_quick_heat_prepare.restype = ctypes.c_int
+    lib.lsr_quick_heat_run.argtypes = [_vp, ctypes.c_int, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float,
+                                                                                     _vp, _vp]
+    lib.lsr_quick_heat_run.restype = ctypes.c_int
+    lib.lsr_heat_frame.argtypes = [_vp] * 4 + [ctypes.c_int] * 4 + [ctypes.c_float] * 3 + [_vp, _vp]
+    lib.lsr_heat_frame.restype = ctypes.c_int
     lib.lsr_query_post_workspace_bytes.argtypes = [ctypes.c_int] * 3
     lib.lsr_query_post_workspace_bytes.restype = ctypes.c_size_t
     lib.lsr_query_smooth.argtypes = [_vp] + [ctypes.c_int] * 4 + [_vp] * 6

@@ -149,6 +149,55 @@ int lsr_quick_query_run(const float* weight_map, int weight_layout, const void* 
     return LSR_OK;
 }
 
+size_t lsr_quick_heat_plan_bytes(int L, int K, int Df, int n_pos, int n_neg)
+{
+    if (codebook_args(L, K, Df) != LSR_OK || L > 3 || n_pos < 1 || n_neg < 0 || n_pos + n_neg > 64) return 0;
+    return quick_heat_plan_bytes(L, K, n_pos, n_neg);
+}
+
+int lsr_quick_heat_prepare(const float* codebooks, const float* pos, const float* neg, int L, int K, int Df,
+                           int n_pos, int n_neg, void* plan, void* stream)
+{
+    if (n_pos < 1 || n_neg < 0) return LSR_EINVAL;
+    LSR_TRY(codebook_args(L, K, Df));
+    if (L > 3 || n_pos + n_neg > 64) return LSR_EUNSUPPORTED;
+    if (L == 0) return LSR_OK;
+    if (!codebooks || !pos || (n_neg > 0 && !neg) || !plan) return LSR_EINVAL;
+    LSR_HIP(launch_quick_heat_prepare(codebooks, pos, neg, L, K, Df, n_pos, n_neg, plan, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_quick_heat_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int n_pos, int n_neg,
+                       int H, int W, int mode, float scale, float eps, float* out, void* stream)
+{
+    if (L < 0 || H < 0 || W < 0 || n_pos < 1 || n_neg < 0 || !layout_ok(weight_layout)) return LSR_EINVAL;
+    if (mode != LSR_HEAT_SUMMED_COSINE && mode != LSR_HEAT_MEAN_RELEVANCY) return LSR_EINVAL;
+    if (!(scale >= 0.f)) return LSR_EINVAL;
+    const bool mean = mode == LSR_HEAT_MEAN_RELEVANCY;
+    if (K != 64 || L > 3 || n_pos + n_neg > 64 || (mean && n_neg < 1)) return LSR_EUNSUPPORTED;
+    if (L == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!weight_map || !plan || !out) return LSR_EINVAL;
+    const bool hwc = weight_layout == LSR_LAYOUT_HWC;
+    // the pixel-major map is read in 16-B pieces
+    if (hwc && misaligned16(weight_map)) return LSR_EUNSUPPORTED;
+    LSR_HIP(launch_quick_heat_run(weight_map, hwc, plan, L, K, n_pos, n_neg, H, W, mean, scale, eps, out,
+                                  (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_heat_frame(const float* maps, const float* stats, const float* rgb, const uint8_t* lut, int planes, int H, int W,
+                   int curve, float threshold, float min_range, float alpha, uint8_t* out, void* stream)
+{
+    if (planes < 0 || H < 0 || W < 0 || (curve != LSR_CURVE_UPPER_HALF && curve != LSR_CURVE_POWER4)) return LSR_EINVAL;
+    if (!(alpha >= 0.f && alpha <= 1.f)) return LSR_EINVAL;
+    if (!heat_frame_shape_ok(planes, H, W)) return LSR_EUNSUPPORTED;
+    if (planes == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!maps || !stats || !lut || !out) return LSR_EINVAL;
+    LSR_HIP(launch_heat_frame(maps, stats, rgb, lut, planes, H, W, curve == LSR_CURVE_POWER4, threshold, min_range,
+                              alpha, out, (hipStream_t)stream));
+    return LSR_OK;
+}
+
 size_t lsr_query_post_workspace_bytes(int planes, int H, int W)
 {
     return query_post_workspace_bytes(planes, H, W);

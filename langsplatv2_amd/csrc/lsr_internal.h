@@ -224,6 +224,21 @@ hipError_t launch_quick_query_prepare(const float* cb, const float* pos, const f
                                       int n_pos, int n_neg, void* ws, hipStream_t st);
 hipError_t launch_quick_query_run(const float* wmap, bool hwc, const void* ws, int L, int K, int n_pos, int n_neg,
                                   int H, int W, bool relevancy, float scale, float eps, float* out, hipStream_t st);
+// the f32 projections P (L, K, ncp) = CB_l E^T the heat plan shares: columns = the negatives, the positives, zeros
+void launch_query_project(const float* cb, const float* pos, const float* neg, int L, int K, int Df, int n_pos,
+                          int n_neg, int ncp, float* P, hipStream_t st);
+
+// quick_heat.hip: the viewer's maps (summed-level cosine / mean relevancy, (n_pos, H, W); K = 64, L <= 3,
+// n_pos + n_neg <= 64) and the colour stage (gate, curve, table, blend with rgb, uint8 (planes, H, W, 3))
+size_t quick_heat_plan_bytes(int L, int K, int n_pos, int n_neg);
+hipError_t launch_quick_heat_prepare(const float* cb, const float* pos, const float* neg, int L, int K, int Df,
+                                     int n_pos, int n_neg, void* ws, hipStream_t st);
+hipError_t launch_quick_heat_run(const float* wmap, bool hwc, const void* ws, int L, int K, int n_pos, int n_neg,
+                                 int H, int W, bool mean, float scale, float eps, float* out, hipStream_t st);
+bool heat_frame_shape_ok(int planes, int H, int W);
+hipError_t launch_heat_frame(const float* maps, const float* stats, const float* rgb, const uint8_t* lut, int planes,
+                             int H, int W, bool power4, float threshold, float min_range, float alpha, uint8_t* out,
+                             hipStream_t st);
 
 // query_post.hip: smoothing, masks and localisation of (planes, H, W) relevancy maps
 bool query_post_shape_ok(int planes, int H, int W);

@@ -1,8 +1,8 @@
-// quick_common.h — what the two consumers of the quick language map share:
-// quick_decode.hip (codebook decode) and quick_query.hip
-// (fused text-query relevancy).  Both are split-f16 MFMA products on the same
-// A fragments: every f32 operand x is split into x_hi = f16(x),
-// x_lo = f16(x - x_hi) (22 significant bits together) and
+// quick_common.h — what the consumers of the quick language map share:
+// quick_decode.hip (codebook decode), quick_query.hip
+// (fused text-query relevancy) and quick_heat.hip (the viewer's maps).  All
+// are split-f16 MFMA products on the same A fragments: every f32 operand x is
+// split into x_hi = f16(x), x_lo = f16(x - x_hi) (22 significant bits together) and
 //   F = W_hi C_hi + W_hi C_lo + W_lo C_hi
 // runs on v_mfma_f32_16x16x32_f16 with f32 accumulation: the products are
 // exact in f32, the dropped W_lo C_lo term is <= 2^-22 |W||C|, i.e. within a
@@ -80,18 +80,20 @@ __device__ __forceinline__ void dec_swap_lanebit(f32x4q& X, f32x4q& Y)
 // The tile front end of the level-resident kernels (k_quick_decode_l, k_quick_query).
 // dec_load_tile: raw weights of 64-pixel tile tt of level l (a tile past the last reads
 // tile 0 and gives zeros): lane (li, lg) holds raw[pb][s][j] = W[64 l + 32 s + 8 lg + j][x = bx + 16 pb + li].
+// PB: the tile's 16-pixel blocks (the level-resident kernels' 4; k_quick_heat's tiles are narrower), nbx
+// the 16 PB-pixel tiles of an image row.
 // HWC: the weight map is pixel-major (H, W, lk) (LSR_LAYOUT_HWC): a lane's 8 codes
 // of one pixel are 32 contiguous bytes, two 16-B loads instead of eight 4-B ones
 // from eight channel planes.
-template <bool HWC>
-__device__ __forceinline__ void dec_load_tile(float (&raw)[4][2][8], const float* __restrict__ wmap, int tt, int ntile,
+template <bool HWC, int PB = 4>
+__device__ __forceinline__ void dec_load_tile(float (&raw)[PB][2][8], const float* __restrict__ wmap, int tt, int ntile,
                                               int nbx, int W, size_t HW, int l, int lk, int li, int lg)
 {
     const bool ok = tt < ntile;
     const int tq = ok ? tt : 0;
-    const int bx = (tq % nbx) * 64, y = tq / nbx;
+    const int bx = (tq % nbx) * (16 * PB), y = tq / nbx;
 #pragma unroll
-    for (int pb = 0; pb < 4; pb++) {
+    for (int pb = 0; pb < PB; pb++) {
         const int xa = bx + 16 * pb + li;
         const size_t pa = (size_t)y * W + min(xa, W - 1);
         const bool in = ok && xa < W;
@@ -127,7 +129,7 @@ __device__ __forceinline__ void dec_load_tile(float (&raw)[4][2][8], const float
 // range (exact: the caller undoes the scale, and the L2 norm is scale-
 // invariant).  Lane (li, lg) holds pixel (pb, li); psc[pb] = 2^e of that
 // pixel: w = psc * w_scaled.
-// k_quick_query calls this; k_quick_decode_l keeps the same statements written
+// k_quick_query and k_quick_heat call this; k_quick_decode_l keeps the same statements written
 // out in its tile loop, and a fix here must be made there too.  Calling it
 // from the decode changes the compiler's code for all eight instantiations
 // (the split comes out as packed v_pk_add_f32 / SDWA converts, fewer
@@ -139,10 +141,12 @@ __device__ __forceinline__ void dec_load_tile(float (&raw)[4][2][8], const float
 // helpers without __restrict__ or split in two compile to the same code
 // (profiles/quick_split_ab_decode.txt).  dec_load_tile is shared by both:
 // through a lambda the decode's code is instruction for instruction the same.
-__device__ __forceinline__ void dec_scale_split(float (&raw)[4][2][8], float (&psc)[4], h8 (&Wh)[4][2], h8 (&Wl)[4][2])
+template <int PB>
+__device__ __forceinline__ void dec_scale_split(float (&raw)[PB][2][8], float (&psc)[PB], h8 (&Wh)[PB][2],
+                                                h8 (&Wl)[PB][2])
 {
 #pragma unroll
-    for (int pb = 0; pb < 4; pb++) {
+    for (int pb = 0; pb < PB; pb++) {
         float m = 0.f;
 #pragma unroll
         for (int s2 = 0; s2 < 2; s2++)
@@ -163,7 +167,7 @@ __device__ __forceinline__ void dec_scale_split(float (&raw)[4][2][8], float (&p
             for (int j = 0; j < 8; j++) raw[pb][s2][j] *= inv;
     }
 #pragma unroll
-    for (int pb = 0; pb < 4; pb++)
+    for (int pb = 0; pb < PB; pb++)
 #pragma unroll
         for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll

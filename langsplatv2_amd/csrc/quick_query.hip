@@ -198,6 +198,13 @@ static QueryPlan query_plan_layout(void* ws, int L, int K, int ncp)
     return q;
 }
 
+void launch_query_project(const float* cb, const float* pos, const float* neg, int L, int K, int Df, int n_pos,
+                          int n_neg, int ncp, float* P, hipStream_t st)
+{
+    k_query_project<<<dim3((unsigned)((K * ncp + 255) / 256), (unsigned)L), 256, 0, st>>>(cb, pos, neg, K, Df, n_pos,
+                                                                                        n_neg, ncp, P);
+}
+
 static int query_ncp(int n_pos, int n_neg) { return (n_pos + n_neg + 15) / 16 * 16; }
 
 size_t quick_query_plan_bytes(int L, int K, int n_pos, int n_neg)
@@ -211,8 +218,7 @@ hipError_t launch_quick_query_prepare(const float* cb, const float* pos, const f
     if (L == 0) return hipSuccess;
     const int ncp = query_ncp(n_pos, n_neg);
     const QueryPlan q = query_plan_layout(ws, L, K, ncp);
-    k_query_project<<<dim3((unsigned)((K * ncp + 255) / 256), (unsigned)L), 256, 0, st>>>(cb, pos, neg, K, Df, n_pos,
-                                                                                        n_neg, ncp, q.P);
+    launch_query_project(cb, pos, neg, L, K, Df, n_pos, n_neg, ncp, q.P, st);
     launch_codebook_frag(q.P, L, K, ncp, q.pfrag, q.pscales, st);
     norm_factor_prepare(cb, L, K, Df, q.G, q.Lf, q.nfrag, q.nscales, true, st);
     return hipGetLastError();

@@ -103,7 +103,10 @@ class _OverlapStream:
     (non-blocking) HIP stream: frame i's result comes back from the push of
     frame i + 1 (or from `flush`), made safe to use on the caller's stream.
     Subclasses give `_alloc(wm)` (the output tensor for a weight map) and
-    `_run(wm, out)` (enqueue the consumer on the current stream)."""
+    `_run(wm, out)` (enqueue the consumer on the current stream).  A consumer
+    that reads more of the render than the weight map overrides `_split`
+    (what render_fn returns -> the weight map and a tuple of further tensors,
+    which `_run` receives after `out`)."""
 
     def __init__(self, device):
         from ._lib import nonblocking_stream
@@ -116,7 +119,7 @@ class _OverlapStream:
         (L*K, H, W) weight map) and queue its consumer; returns the previous
         view's result, or None for the first view."""
         with torch.no_grad():
-            wm = render_fn()
+            wm, extra = self._split(render_fn())
         cur = torch.cuda.current_stream(wm.device)
         rendered = torch.cuda.Event()
         rendered.record(cur)
@@ -126,13 +129,18 @@ class _OverlapStream:
         out = self._alloc(wm)
         with torch.cuda.stream(self._decode_stream):
             self._decode_stream.wait_event(rendered)
-            self._run(wm, out)
+            self._run(wm, out, *extra)
             done = torch.cuda.Event()
             done.record(self._decode_stream)
         wm.record_stream(self._decode_stream)    # the map stays allocated until its consumer ran
+        for t in extra:
+            t.record_stream(self._decode_stream)
         out.record_stream(self._decode_stream)
         self._pending = (out, done)
         return prev
+
+    def _split(self, rendered):
+        return rendered, ()
 
     def flush(self) -> torch.Tensor | None:
         """The last pushed view's result (None if there is none pending)."""

@@ -162,6 +162,45 @@ TABLE = [
     ("lsr_quick_query_run", (None, 1, None, 0, 64, 1, 0, 4, 4, 1, -1.0, 1e-10, None, None), OK),
     ("lsr_quick_query_run", (None, 0, None, 3, 64, 1, 1, 4, 4, 0, 10.0, 1e-10, None, None), EINVAL),
     ("lsr_quick_query_run", (ODD, 1, P, 3, 64, 1, 1, 4, 4, 0, 10.0, 1e-10, P, None), EUNSUP),
+    # lsr_quick_heat_prepare(cb, pos, neg, L, K, Df, n_pos, n_neg, plan, stream)
+    ("lsr_quick_heat_prepare", (None, None, None, 3, 64, 17, 1, 1, None, None), EINVAL),
+    ("lsr_quick_heat_prepare", (None, None, None, 3, 64, 512, 0, 1, None, None), EINVAL),
+    ("lsr_quick_heat_prepare", (None, None, None, 3, 32, 512, 1, 1, None, None), EUNSUP),
+    ("lsr_quick_heat_prepare", (None, None, None, 4, 64, 512, 1, 1, None, None), EUNSUP),
+    ("lsr_quick_heat_prepare", (None, None, None, 3, 64, 512, 33, 32, None, None), EUNSUP),
+    ("lsr_quick_heat_prepare", (None, None, None, 4, 64, 17, 1, 1, None, None), EINVAL),   # both
+    ("lsr_quick_heat_prepare", (None, None, None, 0, 64, 512, 1, 1, None, None), OK),
+    ("lsr_quick_heat_prepare", (None, None, None, 3, 64, 512, 1, 1, None, None), EINVAL),
+    ("lsr_quick_heat_prepare", (P, P, None, 3, 64, 512, 1, 1, P, None), EINVAL),
+    # lsr_quick_heat_run(wmap, layout, plan, L, K, n_pos, n_neg, H, W, mode, scale, eps, out, stream)
+    ("lsr_quick_heat_run", (None, 2, None, 3, 64, 1, 1, 4, 4, 0, 10.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_heat_run", (None, 0, None, 3, 64, 1, 1, 4, 4, 2, 10.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_heat_run", (None, 0, None, 3, 64, 1, 1, 4, 4, 1, -1.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_heat_run", (None, 0, None, 3, 64, 1, 0, 4, 4, 0, NAN, 1e-10, None, None), EINVAL),
+    ("lsr_quick_heat_run", (None, 0, None, 3, 64, 0, 1, 4, 4, 0, 10.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_heat_run", (None, 0, None, 3, 32, 1, 1, 4, 4, 0, 10.0, 1e-10, None, None), EUNSUP),
+    ("lsr_quick_heat_run", (None, 0, None, 4, 64, 1, 1, 4, 4, 0, 10.0, 1e-10, None, None), EUNSUP),
+    ("lsr_quick_heat_run", (None, 0, None, 3, 64, 1, 0, 4, 4, 1, 10.0, 1e-10, None, None), EUNSUP),
+    ("lsr_quick_heat_run", (None, 0, None, 3, 64, 40, 30, 4, 4, 0, 10.0, 1e-10, None, None), EUNSUP),
+    ("lsr_quick_heat_run", (None, 5, None, 4, 64, 1, 1, 4, 4, 0, 10.0, 1e-10, None, None), EINVAL),   # both
+    ("lsr_quick_heat_run", (None, 0, None, 4, 64, 1, 1, 0, 4, 0, 10.0, 1e-10, None, None), EUNSUP),   # before the no-op
+    ("lsr_quick_heat_run", (None, 0, None, 3, 64, 1, 0, 0, 4, 0, 0.0, 1e-10, None, None), OK),
+    ("lsr_quick_heat_run", (None, 1, None, 0, 64, 1, 1, 4, 4, 1, 10.0, 1e-10, None, None), OK),
+    ("lsr_quick_heat_run", (None, 0, None, 3, 64, 1, 0, 4, 4, 0, 0.0, 1e-10, None, None), EINVAL),
+    ("lsr_quick_heat_run", (ODD, 1, P, 3, 64, 1, 0, 4, 4, 0, 0.0, 1e-10, P, None), EUNSUP),
+    # lsr_heat_frame(maps, stats, rgb, lut, planes, H, W, curve, threshold, min_range, alpha, out, stream)
+    ("lsr_heat_frame", (None, None, None, None, -1, 4, 4, 0, 0.22, 0.02, 0.5, None, None), EINVAL),
+    ("lsr_heat_frame", (None, None, None, None, 1, 4, 4, 2, 0.22, 0.02, 0.5, None, None), EINVAL),
+    ("lsr_heat_frame", (None, None, None, None, 1, 4, 4, 0, 0.22, 0.02, -0.1, None, None), EINVAL),
+    ("lsr_heat_frame", (None, None, None, None, 1, 4, 4, 1, 0.22, 0.02, 1.5, None, None), EINVAL),
+    ("lsr_heat_frame", (None, None, None, None, 1, 4, 4, 0, 0.22, 0.02, NAN, None, None), EINVAL),
+    ("lsr_heat_frame", (None, None, None, None, 70000, 4, 4, 0, 0.22, 0.02, 0.5, None, None), EUNSUP),
+    ("lsr_heat_frame", (None, None, None, None, 1, 65536, 65536, 0, 0.22, 0.02, 0.5, None, None), EUNSUP),
+    ("lsr_heat_frame", (None, None, None, None, 70000, 4, 4, 0, 0.22, 0.02, 2.0, None, None), EINVAL),   # both
+    ("lsr_heat_frame", (None, None, None, None, 0, 4, 4, 1, 0.22, 0.0, 1.0, None, None), OK),
+    ("lsr_heat_frame", (None, None, None, None, 2, 4, 0, 0, 0.22, 0.02, 0.0, None, None), OK),
+    ("lsr_heat_frame", (None, None, None, None, 1, 4, 4, 0, 0.22, 0.02, 0.5, None, None), EINVAL),
+    ("lsr_heat_frame", (P, P, None, P, 1, 4, 4, 0, 0.22, 0.02, 0.5, None, None), EINVAL),
     # lsr_query_smooth(rel, planes, H, W, kernel, avg, blend, stats, loc, workspace, stream)
     ("lsr_query_smooth", (None, 2, 4, 4, 4, None, None, None, None, None, None), EINVAL),
     ("lsr_query_smooth", (None, 2, 4, 4, 0, None, None, None, None, None, None), EINVAL),
@@ -274,6 +313,11 @@ for args, some in [((3, 64, 512, 1, 1), True), ((3, 64, 512, 64, 0), True), ((3,
                    ((3, 64, 17, 1, 1), False), ((3, 64, 0, 1, 1), False), ((-1, 64, 512, 1, 1), False),
                    ((3, 64, 512, 0, 1), False), ((3, 64, 512, 1, -1), False), ((3, 64, 512, 33, 32), False)]:
     assert (lib.lsr_quick_query_plan_bytes(*args) > 0) == some, args
+    calls += 1
+for args, some in [((3, 64, 512, 1, 0), True), ((1, 64, 16, 60, 4), True), ((4, 64, 512, 1, 1), False),
+                   ((3, 32, 512, 1, 1), False), ((3, 64, 500, 1, 1), False), ((3, 64, 512, 61, 4), False),
+                   ((3, 64, 512, 0, 1), False)]:
+    assert (lib.lsr_quick_heat_plan_bytes(*args) > 0) == some, args
     calls += 1
 for args, some in [((3, 64, 512, 0), True), ((-1, 64, 512, 1), False), ((3, 64, 24, 1), False), ((3, 128, 512, 1), False)]:
     assert (lib.lsr_quick_decode_plan_bytes(*args) > 0) == some, args
