@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_quick_heat_plan_bytes / _prepare / _run, lsr_heat_frame;
+#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_photo_loss_forward / _backward;
+                               12, additive (no bump): lsr_quick_heat_plan_bytes / _prepare / _run, lsr_heat_frame;
                                12, additive (no bump): lsr_query_post_workspace_bytes, lsr_query_smooth, lsr_query_mask;
                                12, additive (no bump): lsr_quick_query_plan_bytes / _prepare / _run;
                                12 (r06): LSR_OPT_DETERMINISTIC;
@@ -423,6 +424,28 @@ int lsr_lang_loss_backward(const float* weight_map, const float* codebooks, int 
                            const int32_t* seg, const float* features, int S, const float* pixel_stats,
                            const float* grad_loss, float* grad_weight_map, float* grad_codebooks, lsr_alloc_fn alloc,
                            void* alloc_ctx, void* stream);
+
+/* Photometric loss of the RGB training step (train.py:170-173,
+ * utils/loss_utils.py:18-71): image and gt are planes = B*C contiguous fp32
+ * planes of H x W.  Forward writes out[0] = mean |image - gt| and out[1] = mean
+ * SSIM (11-tap Gaussian window, sigma 1.5, zero padding of 5, C1 = 1e-4,
+ * C2 = 9e-4), both over planes*H*W and bit-identical from run to run, and, when
+ * partials is given, the per-pixel derivative maps (3, planes, H, W) the
+ * backward gathers from.  Backward writes
+ *   grad_image = grad_out[0] d out[0]/d image + grad_out[1] d out[1]/d image
+ * (sign(0) = 0) with grad_out a device float[2]; nothing flows to gt.
+ * The caller's loss is (1 - lambda) out[0] + lambda (1 - out[1]).
+ *
+ * LSR_EINVAL: planes, H or W < 1, a NULL image, gt, out or alloc (forward), a
+ * NULL partials, grad_out or grad_image (backward); LSR_EUNSUPPORTED:
+ * planes*H*W >= 2^31; LSR_ENOMEM: alloc returned NULL.  Workspace via alloc
+ * (LSR_BUF_LOSS).  Additive to ABI 12. */
+int lsr_photo_loss_forward(const float* image, const float* gt, int planes, int H, int W,
+                           float* out /* [2]: mean |x-y|, mean SSIM */, float* partials /* (3, planes, H, W) or NULL */,
+                           lsr_alloc_fn alloc, void* alloc_ctx, void* stream);
+int lsr_photo_loss_backward(const float* image, const float* gt, int planes, int H, int W,
+                            const float* partials, const float* grad_out /* device float[2] */,
+                            float* grad_image, void* stream);
 
 /* Fused Adam step: the update of torch.optim.Adam as the
  * reference builds it (scene/gaussian_model.py:234-255, no amsgrad), one pass

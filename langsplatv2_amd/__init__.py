@@ -9,6 +9,7 @@ liblsr.so (C ABI: include/lsr.h).
 from ._lib import deterministic, set_deterministic  # noqa: F401
 from .heatmap import (QuickHeatStream, heat_frames, heat_plan, jet_lut, mean_relevancy_maps,  # noqa: F401
                       summed_similarity_maps)
+from .photo_loss import l1_ssim, photometric_loss  # noqa: F401
 from .query import QuickRelevancyStream, query_plan, relevancy_maps, similarity_maps  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: F401
                          rasterize_gaussians)
@@ -18,4 +19,5 @@ from .segment import (LocalizeResult, SegmentResult, hits, localize_maps, segmen
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "deterministic",
            "set_deterministic", "relevancy_maps", "similarity_maps", "query_plan", "QuickRelevancyStream",
            "smooth_maps", "segment_maps", "localize_maps", "hits", "SegmentResult", "LocalizeResult",
-           "summed_similarity_maps", "mean_relevancy_maps", "heat_frames", "jet_lut", "heat_plan", "QuickHeatStream"]
+           "summed_similarity_maps", "mean_relevancy_maps", "heat_frames", "jet_lut", "heat_plan", "QuickHeatStream",
+           "photometric_loss", "l1_ssim"]

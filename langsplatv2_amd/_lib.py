@@ -133,7 +133,7 @@ EXPORTS = ("lsr_forward", "lsr_backward", "lsr_mark_visible", "lsr_quick_decode"
            "lsr_quick_query_run", "lsr_quick_heat_plan_bytes", "lsr_quick_heat_prepare", "lsr_quick_heat_run",
            "lsr_heat_frame", "lsr_query_post_workspace_bytes", "lsr_query_smooth", "lsr_query_mask",
            "lsr_quick_pack_codes", "lsr_topk_code_forward",
-           "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_adam_step", "lsr_sh_grad_from_views", "lsr_strerror",
+           "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_photo_loss_forward", "lsr_photo_loss_backward", "lsr_adam_step", "lsr_sh_grad_from_views", "lsr_strerror",
            "lsr_abi_version", "lsr_max_lang_dim", "lsr_profile_enable", "lsr_profile_stages", "lsr_profile_reset",
            "lsr_profile_query", "lsr_set_option", "lsr_get_option", "lsr_stream_create", "lsr_stream_destroy")
 
@@ -217,6 +217,10 @@ def load(path: str | None = None):
     lib.lsr_lang_loss_backward.argtypes = [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp,
                                            ALLOC_FN, _vp, _vp]
     lib.lsr_lang_loss_backward.restype = ctypes.c_int
+    lib.lsr_photo_loss_forward.argtypes = [_vp, _vp, _ci, _ci, _ci, _vp, _vp, ALLOC_FN, _vp, _vp]
+    lib.lsr_photo_loss_forward.restype = ctypes.c_int
+    lib.lsr_photo_loss_backward.argtypes = [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]
+    lib.lsr_photo_loss_backward.restype = ctypes.c_int
     _cd = ctypes.c_double
     lib.lsr_adam_step.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int64, _cd, _cd, _cd, _cd, _cd, ctypes.c_int64, _vp]
     lib.lsr_adam_step.restype = ctypes.c_int

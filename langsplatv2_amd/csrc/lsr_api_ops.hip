@@ -29,6 +29,25 @@ int lang_loss_args(const float* wm, const float* cb, int K, int Df, int H, int W
     return LSR_OK;
 }
 
+int photo_loss_args(const float* image, const float* gt, int planes, int H, int W)
+{
+    if (planes < 1 || H < 1 || W < 1 || !image || !gt) return LSR_EINVAL;
+    const int64_t rows = (int64_t)planes * H;   // 32-bit element offsets: planes H W < 2^31
+    return rows > 0x7fffffffLL || rows * W > 0x7fffffffLL ? LSR_EUNSUPPORTED : LSR_OK;
+}
+
+// utils/loss_utils.py:31-33 gaussian(11, 1.5), bit for bit: exp per tap in double, held in
+// an fp32 tensor, so the sum (torch's: the correctly rounded one) and the division are fp32
+PhotoTaps photo_taps()
+{
+    PhotoTaps t;
+    double sum = 0.0;
+    for (int i = 0; i < 11; i++) sum += t.w[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
+    const float fsum = (float)sum;
+    for (int i = 0; i < 11; i++) t.w[i] = t.w[i] / fsum;
+    return t;
+}
+
 // a code count the kernels are not built for is unsupported, anything else invalid
 int topk_code_args(int64_t N, int L, int K, int k)
 {
@@ -253,6 +272,27 @@ int lsr_lang_loss_backward(const float* weight_map, const float* codebooks, int 
     if (!ws) return LSR_ENOMEM;
     LSR_HIP(launch_lang_loss(weight_map, codebooks, Df, H, W, seg, features, S, grad_loss, nullptr, grad_weight_map,
                              grad_codebooks, const_cast<float*>(pixel_stats), ws, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_photo_loss_forward(const float* image, const float* gt, int planes, int H, int W, float* out, float* partials,
+                           lsr_alloc_fn alloc, void* alloc_ctx, void* stream)
+{
+    if (!out || !alloc) return LSR_EINVAL;
+    LSR_TRY(photo_loss_args(image, gt, planes, H, W));
+    void* ws = alloc(alloc_ctx, photo_loss_workspace_bytes(planes, H, W), LSR_BUF_LOSS);
+    if (!ws) return LSR_ENOMEM;
+    LSR_HIP(launch_photo_loss_fwd(image, gt, planes, H, W, photo_taps(), out, partials, ws, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_photo_loss_backward(const float* image, const float* gt, int planes, int H, int W, const float* partials,
+                            const float* grad_out, float* grad_image, void* stream)
+{
+    if (!partials || !grad_out || !grad_image) return LSR_EINVAL;
+    LSR_TRY(photo_loss_args(image, gt, planes, H, W));
+    LSR_HIP(launch_photo_loss_bwd(image, gt, planes, H, W, photo_taps(), partials, grad_out, grad_image,
+                                  (hipStream_t)stream));
     return LSR_OK;
 }
 

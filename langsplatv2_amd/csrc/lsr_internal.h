@@ -262,6 +262,18 @@ hipError_t launch_lang_loss(const float* wmap, const float* cb, int Df, int H, i
                             const float* feat, int S, const float* gscale, float* loss, float* gw, float* dcb,
                             float* stats, float* ws, hipStream_t st);
 
+// photo_loss.hip: L1 + SSIM of (planes, H, W) images (planes H W < 2^31)
+struct PhotoTaps {
+    float w[11];   // the normalised 1-D window (sigma 1.5), formed in double and rounded once
+};
+size_t photo_loss_workspace_bytes(int planes, int H, int W);
+// out[0] = mean |x - y|, out[1] = mean SSIM; partials (3, planes, H, W) or nullptr
+hipError_t launch_photo_loss_fwd(const float* x, const float* y, int planes, int H, int W, const PhotoTaps& tp,
+                                 float* out, float* partials, void* ws, hipStream_t st);
+// gx = g[0] dL1/dx + g[1] dSSIM/dx from the forward's partials (g: device float[2])
+hipError_t launch_photo_loss_bwd(const float* x, const float* y, int planes, int H, int W, const PhotoTaps& tp,
+                                 const float* partials, const float* g, float* gx, hipStream_t st);
+
 // aux.hip: debug NaN/Inf guard (flag |= 1 if any element of p[0..n) is not
 // finite) and the quick-input dense expansion / gradient gather
 hipError_t launch_nonfinite(const float* p, size_t n, uint32_t* flag, hipStream_t st);

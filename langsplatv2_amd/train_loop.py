@@ -152,6 +152,14 @@ def view_loss(image: torch.Tensor, gt: torch.Tensor, lambda_dssim: float) -> tor
     return (1.0 - lambda_dssim) * l1_loss(image, gt) + lambda_dssim * (1.0 - ssim(image, gt))
 
 
+def _loss_fn(fused_loss: bool):
+    """The torch `view_loss`, or the fused HIP pair (photo_loss.photometric_loss: same value and gradient)."""
+    if not fused_loss:
+        return view_loss
+    from .photo_loss import photometric_loss
+    return photometric_loss
+
+
 def sh_ramp(gs: GaussianState, iteration: int, window: int, interval: int = 1000):
     """train.py:135-136 (oneupSHdegree when iteration % 1000 == 0) for the window
     of iterations iteration+1 .. iteration+window, applied before its first view."""
@@ -175,8 +183,9 @@ class RGBTrainer:
     the R ranks' gradients and statistics, every rank steps its replica."""
 
     def __init__(self, gs: GaussianState, bg: torch.Tensor, lambda_dssim: float = 0.2, group=None, fused_adam=True,
-                 sh_interval: int = 1000):
+                 sh_interval: int = 1000, fused_loss: bool = False):
         self.gs = gs
+        self.loss_fn = _loss_fn(fused_loss)
         self.sh_interval = sh_interval
         self.bg = bg
         self.lambda_dssim = lambda_dssim
@@ -188,7 +197,7 @@ class RGBTrainer:
     def step(self, cam: dict, gt: torch.Tensor) -> float:
         sh_ramp(self.gs, self.iteration, self.world, self.sh_interval)
         pkg = render_rgb(cam, self.gs, self.bg)
-        loss = view_loss(pkg["render"], gt, self.lambda_dssim)
+        loss = self.loss_fn(pkg["render"], gt, self.lambda_dssim)
         loss.backward()
         params = self.gs.params()
         grads, stats, max_radii = self.exchange.exchange([p.grad for p in params],
@@ -203,16 +212,17 @@ class RGBTrainer:
 
 
 def accumulate_views(gs: GaussianState, opt, cams: list, gts: list, bg: torch.Tensor, lambda_dssim: float = 0.2,
-                     iteration: int = 0, sh_interval: int = 1000):
+                     iteration: int = 0, sh_interval: int = 1000, fused_loss: bool = False):
     """The single-GPU reference of one DP step: `len(cams)` iterations with
     accum_iter = len(cams) (train.py:245-263): per view, backward into .grad
     (autograd accumulates), max_radii2D / densification stats; one optimizer
     step at the end of the window."""
     sh_ramp(gs, iteration, len(cams), sh_interval)
+    loss_fn = _loss_fn(fused_loss)
     losses = []
     for cam, gt in zip(cams, gts):
         pkg = render_rgb(cam, gs, bg)
-        loss = view_loss(pkg["render"], gt, lambda_dssim)
+        loss = loss_fn(pkg["render"], gt, lambda_dssim)
         loss.backward()
         apply_view_stats(gs, pkg["radii"], dp.densify_increment(pkg["viewspace_points"].grad, pkg["radii"]))
         losses.append(float(loss.detach()))
