@@ -456,6 +456,60 @@ int lsr_photo_loss_backward(const float* image, const float* gt, int planes, int
 int lsr_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double lr,
                   double beta1, double beta2, double eps, double weight_decay, int64_t step, void* stream);
 
+/* GaussianModel.densify_and_prune of the RGB phase (scene/gaussian_model.py:352-504,
+ * every 100 iterations, train.py:246-258) as one gather over the six parameter
+ * groups and their Adam moments.  Groups, in this order, all fp32 row-major with
+ * N rows: xyz (3), f_dc (3), f_rest (rest_width = 3 (coeffs - 1)), opacity (1),
+ * scaling (3, log-scales), rotation (4, raw quaternion).
+ *
+ * Per row i: g = accum / denom with NaN -> 0 (x / 0 = inf stays and is selected),
+ * ms = max_j exp(scaling_j); clone: |g| >= max_grad and ms <= dense_thresh;
+ * split: g >= max_grad and ms > dense_thresh.  A split row is replaced by two
+ * children r = 0, 1: xyz' = build_rotation(rotation) (exp(scaling) * noise[i][r]) + xyz,
+ * scaling' = log(exp(scaling) / 1.6), the rest copied.  Every surviving row
+ * (originals, clones, children with scaling') is dropped when
+ * sigmoid(opacity) < min_opacity, or, with prune_big != 0, when its
+ * max_j exp(scaling_j) > big_thresh.  (The reference zeroes max_radii2D before
+ * its final prune, so its screen-size term never fires; it is not an input.)
+ * Output rows, each segment in input order: kept originals, kept clones, kept
+ * round-0 children, kept round-1 children.  Moments are copied for the first
+ * segment and zero elsewhere.  No atomics: bit-reproducible.
+ *
+ * lsr_densify_plan classifies, scans and fills the row map in workspace
+ * (lsr_densify_workspace_bytes(N) bytes, device, 256-B aligned) and returns in
+ * the host array counts[LSR_DENSIFY_COUNTS] = {the four segment sizes, rows
+ * selected for cloning, rows selected for splitting} after synchronising the
+ * stream (the one host read-back, like lsr_fwd_out.num_rendered).  The caller
+ * sizes the outputs to n_out = counts[0] + .. + counts[3] rows and calls
+ * lsr_densify_apply with the same N and workspace: one launch writes every
+ * non-NULL dst tensor (a NULL dst skips that tensor, e.g. moments of an
+ * optimiser without state; its src is then ignored).  noise is (N, 2, 3)
+ * standard-normal samples indexed by parent row and round.
+ *
+ * LSR_EINVAL: N < 0, rest_width < 0, max_grad <= 0 or NaN (clones must never be
+ * split again), a NULL required pointer, n_out < 0; LSR_EUNSUPPORTED: N > 2^28;
+ * N == 0 (plan: counts all 0) and n_out == 0 (apply) are no-ops.  Additive to ABI 12. */
+#define LSR_DENSIFY_GROUPS 6
+#define LSR_DENSIFY_XYZ 0
+#define LSR_DENSIFY_F_DC 1
+#define LSR_DENSIFY_F_REST 2
+#define LSR_DENSIFY_OPACITY 3
+#define LSR_DENSIFY_SCALING 4
+#define LSR_DENSIFY_ROTATION 5
+#define LSR_DENSIFY_COUNTS 6
+#define LSR_DENSIFY_MAX_ROWS (1LL << 28)
+size_t lsr_densify_workspace_bytes(int64_t N);
+int lsr_densify_plan(int64_t N, const float* accum, const float* denom, const float* scaling, const float* opacity,
+                     float max_grad, float dense_thresh, float min_opacity, int prune_big, float big_thresh,
+                     void* workspace, int64_t* counts /* host [LSR_DENSIFY_COUNTS] */, void* stream);
+int lsr_densify_apply(int64_t N, int64_t n_out, const void* workspace, int rest_width,
+                      const float* const* src /* [3][LSR_DENSIFY_GROUPS]: parameter, exp_avg, exp_avg_sq */,
+                      float* const* dst /* same layout; NULL entries skipped */, const float* noise, void* stream);
+/* GaussianModel.reset_opacity (scene/gaussian_model.py:303-306), in place over n
+ * elements: opacity = inverse_sigmoid(min(sigmoid(opacity), 0.01)), exp_avg and
+ * exp_avg_sq (either may be NULL) zeroed. */
+int lsr_reset_opacity(int64_t n, float* opacity, float* exp_avg, float* exp_avg_sq, void* stream);
+
 /* simple_knn._C.distCUDA2 (scene/gaussian_model.py:20,194): for points
  * (N, 3) fp32, out[i] = mean of the three smallest squared distances
  * dx*dx + dy*dy + dz*dz to points j != i (exact; FLT_MAX for missing

@@ -133,7 +133,8 @@ EXPORTS = ("lsr_forward", "lsr_backward", "lsr_mark_visible", "lsr_quick_decode"
            "lsr_quick_query_run", "lsr_quick_heat_plan_bytes", "lsr_quick_heat_prepare", "lsr_quick_heat_run",
            "lsr_heat_frame", "lsr_query_post_workspace_bytes", "lsr_query_smooth", "lsr_query_mask",
            "lsr_quick_pack_codes", "lsr_topk_code_forward",
-           "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_photo_loss_forward", "lsr_photo_loss_backward", "lsr_adam_step", "lsr_sh_grad_from_views", "lsr_strerror",
+           "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_photo_loss_forward", "lsr_photo_loss_backward",
+           "lsr_densify_workspace_bytes", "lsr_densify_plan", "lsr_densify_apply", "lsr_reset_opacity", "lsr_adam_step", "lsr_sh_grad_from_views", "lsr_strerror",
            "lsr_abi_version", "lsr_max_lang_dim", "lsr_profile_enable", "lsr_profile_stages", "lsr_profile_reset",
            "lsr_profile_query", "lsr_set_option", "lsr_get_option", "lsr_stream_create", "lsr_stream_destroy")
 
@@ -221,6 +222,16 @@ def load(path: str | None = None):
     lib.lsr_photo_loss_forward.restype = ctypes.c_int
     lib.lsr_photo_loss_backward.argtypes = [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]
     lib.lsr_photo_loss_backward.restype = ctypes.c_int
+    _cf, _i64 = ctypes.c_float, ctypes.c_int64
+    lib.lsr_densify_workspace_bytes.argtypes = [_i64]
+    lib.lsr_densify_workspace_bytes.restype = ctypes.c_size_t
+    lib.lsr_densify_plan.argtypes = [_i64, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _ci, _cf, _vp,
+                                     ctypes.POINTER(_i64), _vp]
+    lib.lsr_densify_plan.restype = ctypes.c_int
+    lib.lsr_densify_apply.argtypes = [_i64, _i64, _vp, _ci, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]
+    lib.lsr_densify_apply.restype = ctypes.c_int
+    lib.lsr_reset_opacity.argtypes = [_i64, _vp, _vp, _vp, _vp]
+    lib.lsr_reset_opacity.restype = ctypes.c_int
     _cd = ctypes.c_double
     lib.lsr_adam_step.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int64, _cd, _cd, _cd, _cd, _cd, ctypes.c_int64, _vp]
     lib.lsr_adam_step.restype = ctypes.c_int

@@ -296,6 +296,61 @@ int lsr_photo_loss_backward(const float* image, const float* gt, int planes, int
     return LSR_OK;
 }
 
+size_t lsr_densify_workspace_bytes(int64_t N)
+{
+    return N < 0 || N > LSR_DENSIFY_MAX_ROWS ? 0 : densify_workspace_bytes(N);
+}
+
+int lsr_densify_plan(int64_t N, const float* accum, const float* denom, const float* scaling, const float* opacity,
+                     float max_grad, float dense_thresh, float min_opacity, int prune_big, float big_thresh,
+                     void* workspace, int64_t* counts, void* stream)
+{
+    // max_grad > 0: a clone's padded gradient is 0 and must stay below it
+    if (N < 0 || !(max_grad > 0.f) || !counts) return LSR_EINVAL;
+    if (N > LSR_DENSIFY_MAX_ROWS) return LSR_EUNSUPPORTED;
+    for (int k = 0; k < LSR_DENSIFY_COUNTS; k++) counts[k] = 0;
+    if (N == 0) return LSR_OK;
+    if (!accum || !denom || !scaling || !opacity || !workspace) return LSR_EINVAL;
+    const DensifyArgs a = {max_grad, dense_thresh, min_opacity, big_thresh, prune_big ? 1 : 0};
+    hipStream_t st = (hipStream_t)stream;
+    LSR_HIP(launch_densify_plan(N, accum, denom, scaling, opacity, a, workspace, st));
+    LSR_HIP(hipMemcpyAsync(counts, densify_counts(N, workspace), LSR_DENSIFY_COUNTS * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, st));
+    LSR_HIP(hipStreamSynchronize(st));
+    return LSR_OK;
+}
+
+int lsr_densify_apply(int64_t N, int64_t n_out, const void* workspace, int rest_width, const float* const* src,
+                      float* const* dst, const float* noise, void* stream)
+{
+    if (N < 0 || n_out < 0 || rest_width < 0) return LSR_EINVAL;
+    if (N > LSR_DENSIFY_MAX_ROWS || n_out > 2 * LSR_DENSIFY_MAX_ROWS) return LSR_EUNSUPPORTED;
+    if (N == 0 || n_out == 0) return LSR_OK;
+    if (!workspace || !src || !dst || !noise) return LSR_EINVAL;
+    DensifyTable t;
+    const int width[LSR_DENSIFY_GROUPS] = {3, 3, rest_width, 1, 3, 4};
+    for (int g = 0; g < LSR_DENSIFY_GROUPS; g++) t.width[g] = width[g];
+    for (int k = 0; k < 3 * LSR_DENSIFY_GROUPS; k++) {
+        const bool param = k < LSR_DENSIFY_GROUPS, empty = width[k % LSR_DENSIFY_GROUPS] == 0;
+        // every parameter is read and written (a child's xyz reads scaling and rotation); moments are optional
+        if (!empty && ((param && !dst[k]) || (dst[k] && !src[k]))) return LSR_EINVAL;
+        t.src[k] = src[k];
+        t.dst[k] = empty ? nullptr : dst[k];
+    }
+    t.noise = noise;
+    LSR_HIP(launch_densify_apply(N, n_out, workspace, t, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_reset_opacity(int64_t n, float* opacity, float* exp_avg, float* exp_avg_sq, void* stream)
+{
+    if (n < 0) return LSR_EINVAL;
+    if (n == 0) return LSR_OK;
+    if (!opacity) return LSR_EINVAL;
+    LSR_HIP(launch_reset_opacity(n, opacity, exp_avg, exp_avg_sq, (hipStream_t)stream));
+    return LSR_OK;
+}
+
 int lsr_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double lr,
                   double beta1, double beta2, double eps, double weight_decay, int64_t step, void* stream)
 {

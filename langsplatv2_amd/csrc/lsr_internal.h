@@ -274,6 +274,24 @@ hipError_t launch_photo_loss_fwd(const float* x, const float* y, int planes, int
 hipError_t launch_photo_loss_bwd(const float* x, const float* y, int planes, int H, int W, const PhotoTaps& tp,
                                  const float* partials, const float* g, float* gx, hipStream_t st);
 
+// densify.hip: densify_and_prune as one gather (plan: classify, scan, fill; apply: all 18 tensors)
+struct DensifyArgs {
+    float max_grad, dense_thresh, min_opacity, big_thresh;   // thresholds as the reference's fp32 comparisons see them
+    int prune_big;                                           // max_screen_size truthy
+};
+struct DensifyTable {   // entry part * LSR_DENSIFY_GROUPS + group; part 0 parameter, 1 exp_avg, 2 exp_avg_sq
+    const float* src[3 * LSR_DENSIFY_GROUPS];
+    float* dst[3 * LSR_DENSIFY_GROUPS];   // nullptr: skipped
+    int width[LSR_DENSIFY_GROUPS];
+    const float* noise;                   // (N, 2, 3)
+};
+size_t densify_workspace_bytes(int64_t N);
+hipError_t launch_densify_plan(int64_t N, const float* accum, const float* denom, const float* scaling,
+                               const float* opacity, const DensifyArgs& a, void* ws, hipStream_t st);
+const int64_t* densify_counts(int64_t N, const void* ws);   // device int64[LSR_DENSIFY_COUNTS] inside ws
+hipError_t launch_densify_apply(int64_t N, int64_t n_out, const void* ws, const DensifyTable& t, hipStream_t st);
+hipError_t launch_reset_opacity(int64_t n, float* opacity, float* m, float* v, hipStream_t st);
+
 // aux.hip: debug NaN/Inf guard (flag |= 1 if any element of p[0..n) is not
 // finite) and the quick-input dense expansion / gradient gather
 hipError_t launch_nonfinite(const float* p, size_t n, uint32_t* flag, hipStream_t st);

@@ -23,13 +23,23 @@ same update as `--accum_iter R` on one GPU with the R views in one
 accumulation window (only the gradient summation order differs).  One step
 advances the iteration counter by R; the SH ramp is applied at step
 granularity (all views of a window use the degree active at its first
-iteration, so the replicas stay identical).  densify_and_prune itself (clone /
-split / prune, scene/gaussian_model.py:422-505) is outside the rasterizer path
-and not restated; its inputs (max_radii2D, xyz_gradient_accum, denom) are.
+iteration, so the replicas stay identical).
+
+Adaptive density control (train.py:246-258): with a `DensifyConfig`, RGBTrainer
+runs densify_and_prune (clone / split / prune, scene/gaussian_model.py:422-505)
+and reset_opacity on the reference's schedule, through the fused gather of
+langsplatv2_amd.densify, after the statistics of the window and before its
+optimiser step (the rebound tensors have no gradient, so that step skips them,
+as in the reference).  The schedule is evaluated at window granularity like the
+SH ramp; the decision inputs are the reduced statistics and the split noise
+comes from a generator seeded from (seed, iteration), so the replicas stay
+identical; the exchange is rebuilt over the new tensors.  Without a config
+(the default) the point set keeps its size.
 """
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 
 import torch
 import torch.nn.functional as F
@@ -178,13 +188,50 @@ def apply_view_stats(gs: GaussianState, radii: torch.Tensor, stats: torch.Tensor
     gs.denom += stats[:, 1:2]
 
 
+@dataclass
+class DensifyConfig:
+    """Adaptive density control of train.py:246-258 with OptimizationParams' defaults
+    (arguments/__init__.py).  extent is scene.cameras_extent; seed feeds the split noise."""
+    extent: float
+    densify_from_iter: int = 500
+    densify_until_iter: int = 15000
+    densification_interval: int = 100
+    opacity_reset_interval: int = 3000
+    densify_grad_threshold: float = 0.0002
+    percent_dense: float = 0.01
+    min_opacity: float = 0.005
+    white_background: bool = False
+    seed: int = 0
+    fused: bool = True   # False: densify.densify_and_prune_torch / the torch reset (the A/B baseline)
+
+
+def densify_schedule(cfg: DensifyConfig, iteration: int, window: int):
+    """train.py:248-258 for the window of iterations iteration+1 .. iteration+window: (the iteration whose
+    densify_and_prune fires or None, its size_threshold, whether reset_opacity fires)."""
+    densify_it, reset = None, False
+    for it in range(iteration + 1, iteration + window + 1):
+        if it >= cfg.densify_until_iter:
+            break
+        if densify_it is None and it > cfg.densify_from_iter and it % cfg.densification_interval == 0:
+            densify_it = it
+        if it % cfg.opacity_reset_interval == 0 or (cfg.white_background and it == cfg.densify_from_iter):
+            reset = True
+    size_threshold = 20 if densify_it is not None and densify_it > cfg.opacity_reset_interval else None
+    return densify_it, size_threshold, reset
+
+
 class RGBTrainer:
     """One optimizer step per call: this rank renders `view`, the exchange sums
-    the R ranks' gradients and statistics, every rank steps its replica."""
+    the R ranks' gradients and statistics, every rank steps its replica.
+    densify: a DensifyConfig turns adaptive density control on (None: the point
+    set keeps its size); last_densify is the DensifyResult of the latest one."""
 
     def __init__(self, gs: GaussianState, bg: torch.Tensor, lambda_dssim: float = 0.2, group=None, fused_adam=True,
-                 sh_interval: int = 1000, fused_loss: bool = False):
+                 sh_interval: int = 1000, fused_loss: bool = False, densify: DensifyConfig | None = None):
         self.gs = gs
+        self.densify = densify
+        self.last_densify = None
+        self.group = group
         self.loss_fn = _loss_fn(fused_loss)
         self.sh_interval = sh_interval
         self.bg = bg
@@ -203,12 +250,33 @@ class RGBTrainer:
         grads, stats, max_radii = self.exchange.exchange([p.grad for p in params],
                                                          pkg["viewspace_points"].grad, pkg["radii"])
         apply_view_stats(self.gs, max_radii, stats)
-        for p, g in zip(params, grads):
-            p.grad = g
+        if self.densify is not None:
+            self._density_control()
+        for p_old, p, g in zip(params, self.gs.params(), grads):
+            if p is p_old:   # a tensor density control rebound has no gradient this step (train.py:255-263)
+                p.grad = g
         self.opt.step()
         self.opt.zero_grad(set_to_none=True)
         self.iteration += self.world
         return float(loss.detach())
+
+    def _density_control(self):
+        from . import densify as D
+        cfg = self.densify
+        densify_it, size_threshold, reset = densify_schedule(cfg, self.iteration, self.world)
+        if densify_it is None and not reset:
+            return
+        if densify_it is not None:
+            dev = self.gs.get_xyz.device
+            gen = torch.Generator(device=dev).manual_seed((int(cfg.seed) << 32) + densify_it)
+            self.last_densify = D.densify_and_prune(
+                self.gs, self.opt, max_grad=cfg.densify_grad_threshold, min_opacity=cfg.min_opacity,
+                extent=cfg.extent, max_screen_size=size_threshold, percent_dense=cfg.percent_dense, generator=gen,
+                fused=cfg.fused)
+        if reset:
+            D.reset_opacity(self.gs, self.opt, fused=cfg.fused)
+        self.exchange = dp.ViewShardedExchange(self.gs.params(), with_stats=True, group=self.group,
+                                               names=list(PARAM_NAMES))
 
 
 def accumulate_views(gs: GaussianState, opt, cams: list, gts: list, bg: torch.Tensor, lambda_dssim: float = 0.2,
@@ -362,6 +430,6 @@ def accumulate_language_views(ls: LanguageState, opt, cams: list, segs: list, fe
     return losses
 
 
-__all__ = ["GaussianState", "render_rgb", "sh_ramp", "l1_loss", "ssim", "view_loss", "apply_view_stats", "RGBTrainer",
+__all__ = ["GaussianState", "DensifyConfig", "densify_schedule", "render_rgb", "sh_ramp", "l1_loss", "ssim", "view_loss", "apply_view_stats", "RGBTrainer",
            "accumulate_views", "PARAM_NAMES", "LanguageState", "render_language", "language_view_loss",
            "LanguageTrainer", "accumulate_language_views", "LANG_PARAM_NAMES"]
