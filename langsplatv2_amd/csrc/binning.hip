@@ -27,8 +27,9 @@
 #define LSR_BIN_TARGET 512   // (chunk x band) blocks of the privatised count / scatter
 #endif
 #ifndef LSR_SORT_WAVE_MAX
-#define LSR_SORT_WAVE_MAX 1024  // largest tile sorted by one wave in registers (512, 1024 or 2048): cfg3 tile_sort 0.079 -> 0.073 ms at 1024
+#define LSR_SORT_WAVE_MAX 1024  // largest tile sorted by one wave in registers (512 or 1024): cfg3 tile_sort 0.079 -> 0.073 ms at 1024
 #endif
+static_assert(LSR_SORT_WAVE_MAX == 512 || LSR_SORT_WAVE_MAX == 1024, "the one-wave sort holds at most 16 keys per lane");
 #ifndef LSR_SORT_DPP
 #define LSR_SORT_DPP 1
 #endif
@@ -991,10 +992,12 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_tile_sort_big(int T, const uint3
         tile_sort_big((int)cls_list[(size_t)5 * T + i], tile_start, keys, point_list, buf);
 }
 
-// Wave-level register bitonic sort for tiles of n <= 64*KPL keys: lane l
-// holds elements [l*KPL, l*KPL + KPL) (padding = UINT64_MAX).  Steps whose
-// partner distance j < KPL run inside the lane's registers; the others pair
-// lane l with lane l ^ (j / KPL) through shuffles.  No LDS, no barriers.
+// Wave-level register bitonic sort of a full run of 64*KPL keys (the 4-wave
+// block sort's per-wave runs): lane l holds elements [l*KPL, l*KPL + KPL)
+// (padding = UINT64_MAX).  Steps whose partner distance j < KPL run inside the
+// lane's registers; the others pair lane l with lane l ^ (j / KPL) through
+// lane exchanges.  No LDS, no barriers.  (The one-wave tile sort has its own
+// network, sized by the key count: wave_sort_tile below.)
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m)
 {
     const uint32_t lo = __shfl_xor((uint32_t)v, m, 64);
@@ -1081,6 +1084,82 @@ __device__ __forceinline__ void wave_sort_stages(uint64_t (&v)[KPL])
     }
 }
 
+// The one-wave tile sort (class 0) sizes its network by the tile's key count:
+// KPL = ceil(n / 64) keys per lane, not a power of two (the power-of-two network
+// it replaces ran 1024 slots for cfg3's 487..715 keys).  Lane l holds elements
+// [l*KPL, l*KPL + KPL), +inf from n up.  A merge sort whose runs are lanes:
+//  - every lane sorts its KPL registers (Batcher's odd-even merge sort, which
+//    exists for every length: 32 compare-exchanges at KPL = 10, 63 at 16);
+//  - for m = 2, 4 .. 64 lanes: the flip pairs element (l, r) with
+//    (l ^ (m - 1), KPL - 1 - r), the minimum to the lower lane, which leaves
+//    both halves bitonic and the lower one below the upper; half-cleaners at
+//    lane distances m/4 .. 1 (every register against the same register of
+//    lane l ^ d) then leave every lane a bitonic KPL keys that lie between
+//    its neighbours', and the lane's own sort finishes the stage.
+// The flip and the half-cleaner hold for runs of any equal length, so nothing
+// is padded to a power of two.  21 lane-exchange steps in all (the log2 m of
+// every stage), each over KPL registers, with every partner fetched before
+// every select as in wave_sort_xstep.  Same keys, total order: the output is
+// the full network's.
+template <int KPL>
+__device__ __forceinline__ void lane_sort_regs(uint64_t (&v)[KPL])
+{
+    // odd-even merge sort over v[0, KPL), every index a compile-time constant
+#pragma unroll
+    for (int p = 1; p < KPL; p *= 2) {
+#pragma unroll
+        for (int k = p; k >= 1; k /= 2) {
+#pragma unroll
+            for (int j = k % p; j + k < KPL; j += 2 * k) {
+#pragma unroll
+                for (int i = 0; i < k; i++) {
+                    const int a = i + j, b = i + j + k;
+                    if (b >= KPL || a / (2 * p) != b / (2 * p)) continue;
+                    const uint64_t x = v[a], y = v[b];
+                    const bool sw = x > y;
+                    v[a] = sw ? y : x;
+                    v[b] = sw ? x : y;
+                }
+            }
+        }
+    }
+}
+
+// One lane-exchange step: register r against register (FLIP ? KPL - 1 - r : r)
+// of lane l ^ M; the lane whose bit LOW is clear keeps the minimum.
+template <int KPL, int M, int LOW, bool FLIP>
+__device__ __forceinline__ void wsort_xstep(uint64_t (&v)[KPL])
+{
+    const int lane = threadIdx.x & 63;
+    const bool take_min = (lane & LOW) == 0;
+    uint64_t o[KPL];
+#pragma unroll
+    for (int r = 0; r < KPL; r++) o[r] = xor_lane_u64<M>(v[FLIP ? KPL - 1 - r : r]);
+#pragma unroll
+    for (int r = 0; r < KPL; r++) v[r] = ((v[r] < o[r]) == take_min) ? v[r] : o[r];
+}
+
+template <int KPL, int D>
+__device__ __forceinline__ void wsort_halfclean(uint64_t (&v)[KPL])
+{
+    if constexpr (D >= 1) {
+        wsort_xstep<KPL, D, D, false>(v);
+        wsort_halfclean<KPL, D / 2>(v);
+    }
+}
+
+template <int KPL, int M>
+__device__ __forceinline__ void wsort_merge_lanes(uint64_t (&v)[KPL])
+{
+    if constexpr (M <= 64) {
+        wsort_xstep<KPL, M - 1, M / 2, true>(v);
+        wsort_halfclean<KPL, M / 4>(v);
+        lane_sort_regs<KPL>(v);
+        wsort_merge_lanes<KPL, 2 * M>(v);
+    }
+}
+
+// n <= 64 KPL keys of one tile, sorted by one wave.
 template <int KPL>
 __device__ __forceinline__ void wave_sort_tile(const uint64_t* __restrict__ g, uint32_t* __restrict__ out, int n)
 {
@@ -1091,7 +1170,8 @@ __device__ __forceinline__ void wave_sort_tile(const uint64_t* __restrict__ g, u
         const int e = lane * KPL + r;
         v[r] = e < n ? g[e] : ~0ull;
     }
-    wave_sort_stages<KPL, 2>(v);
+    lane_sort_regs<KPL>(v);
+    wsort_merge_lanes<KPL, 2>(v);
 #pragma unroll
     for (int r = 0; r < KPL; r++) {
         const int e = lane * KPL + r;
@@ -1208,8 +1288,11 @@ __global__ void __launch_bounds__(256) k_tile_sort_blk(int T, const uint32_t* __
     }
 }
 
-// Class 0 (n <= 512): one wave per listed tile, four per workgroup.
-__global__ void __launch_bounds__(256) k_tile_sort_wave(int T, const uint32_t* __restrict__ tile_start,
+// Class 0 (n <= LSR_SORT_WAVE_MAX): one wave per listed tile, four per workgroup.
+// (capped at the 128 VGPRs of 4 waves per SIMD, the occupancy of the power-of-two
+// network it replaces: uncapped the scheduler takes 136)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_tile_sort_wave(int T, const uint32_t* __restrict__ tile_start,
                                                         const uint64_t* __restrict__ keys,
                                                         uint32_t* __restrict__ point_list,
                                                         const uint32_t* __restrict__ cls_cnt,
@@ -1222,14 +1305,26 @@ __global__ void __launch_bounds__(256) k_tile_sort_wave(int T, const uint32_t* _
         const int n = (int)(tile_start[t + 1] - s0);
         const uint64_t* g = keys + s0;
         uint32_t* o = point_list + s0;
+        // keys per lane: every count up to 4, even counts above (the odd ones from 5
+        // up spill at the 128 VGPRs of 4 waves per SIMD)
         if (n == 1) {
             if ((threadIdx.x & 63) == 0) o[0] = (uint32_t)g[0];
-        } else if (n <= 64) wave_sort_tile<1>(g, o, n);
-        else if (n <= 128) wave_sort_tile<2>(g, o, n);
-        else if (n <= 256) wave_sort_tile<4>(g, o, n);
-        else if (LSR_SORT_WAVE_MAX <= 512 || n <= 512) wave_sort_tile<8>(g, o, n);
-        else if (LSR_SORT_WAVE_MAX <= 1024 || n <= 1024) wave_sort_tile<16>(g, o, n);
-        else wave_sort_tile<32>(g, o, n);
+            continue;
+        }
+        int kpl = (n + 63) >> 6;
+        if (kpl > 4) kpl = (kpl + 1) & ~1;
+        switch (kpl) {
+        case 1: wave_sort_tile<1>(g, o, n); break;
+        case 2: wave_sort_tile<2>(g, o, n); break;
+        case 3: wave_sort_tile<3>(g, o, n); break;
+        case 4: wave_sort_tile<4>(g, o, n); break;
+        case 6: wave_sort_tile<6>(g, o, n); break;
+        case 8: wave_sort_tile<8>(g, o, n); break;
+        case 10: wave_sort_tile<10>(g, o, n); break;
+        case 12: wave_sort_tile<12>(g, o, n); break;
+        case 14: wave_sort_tile<14>(g, o, n); break;
+        default: wave_sort_tile<16>(g, o, n); break;
+        }
     }
 }
 
