@@ -12,9 +12,6 @@ namespace lsr {
 #ifndef LSR_BAND_LDS
 #define LSR_BAND_LDS 32768
 #endif
-#ifndef LSR_COUNT_XCD
-#define LSR_COUNT_XCD 1   // chunk-major count grid: cfg5 bin_count 0.627 -> 0.604 ms (cfg3 ±0)
-#endif
 struct Band {
     int ty0, ty1, t0, nt;
     __device__ Band(const Cam& c, int rows, int band)

@@ -1,5 +1,5 @@
-// binning.hip — tile binning (A.2): per-tile instance counts, scatter into
-// tile buckets, per-tile depth sort.
+// binning.hip — tile binning (A.2): per-tile instance counts and the scatter
+// into tile buckets; the per-tile depth sort that follows is tile_sort.hip.
 //
 // MI355X design (vs the reference's global 64-bit radix sort over
 // 32 + log2(T) bits of M keys): the tile is the bucket.
@@ -8,9 +8,7 @@
 //    ranks inside the block: no global atomics at all.  (The older
 //    k_duplicate / k_scatter pair with one global atomic per instance remains
 //    as the fallback when T does not fit LDS.)
-//  - per-tile sort of the bucket's unique u64 keys (depth bits << 32 | id):
-//    one wave per tile with the keys in registers (k_tile_sort_wave, n <= 1024);
-//    a workgroup in LDS for n <= 4096, chunked LDS + global merge above.
+//  - per-tile sort of the bucket's unique u64 keys (depth bits << 32 | id).
 // The result equals a stable sort by (tile, depth bits) with ties broken by
 // Gaussian id — the order of the reference's stable radix sort over
 // duplicates emitted in Gaussian order — of the reference's instances minus
@@ -20,198 +18,35 @@
 // pixel of its tile, so no output changes (the oracle checks both lists
 // render identically: tests/test_oracle.py).  cfg3: 8.25 M -> 4.73 M.
 #include "bin_common.h"
+#include "scan.h"
+#include "tile_sort.h"
 
 #include <algorithm>
 
 #ifndef LSR_BIN_TARGET
 #define LSR_BIN_TARGET 512   // (chunk x band) blocks of the privatised count / scatter
 #endif
-#ifndef LSR_SORT_WAVE_MAX
-#define LSR_SORT_WAVE_MAX 1024  // largest tile sorted by one wave in registers (512 or 1024): cfg3 tile_sort 0.079 -> 0.073 ms at 1024
-#endif
-static_assert(LSR_SORT_WAVE_MAX == 512 || LSR_SORT_WAVE_MAX == 1024, "the one-wave sort holds at most 16 keys per lane");
-#ifndef LSR_SORT_DPP
-#define LSR_SORT_DPP 1
-#endif
 
 namespace lsr {
 
-// ---------------------------------------------------------------- scan ----
-#define SCAN_ITEMS 16
-#define SCAN_BLOCK 256
-#define SCAN_TILE (SCAN_ITEMS * SCAN_BLOCK)
-
-size_t scan_partials(size_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE + 1; }
-
-// Block-wide exclusive scan over NB threads (sh: NB / 64 entries).
-template <int NB>
-__device__ __forceinline__ uint64_t block_excl_scan_u64_n(uint64_t v, uint64_t* sh, uint64_t& total)
-{
-    // wave inclusive scan via shuffles, then across the waves through LDS
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint64_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) sh[w] = x;
-    __syncthreads();
-    uint64_t wofs = 0, tot = 0;
-    for (int k = 0; k < NB / 64; k++) {
-        if (k < w) wofs += sh[k];
-        tot += sh[k];
-    }
-    __syncthreads();
-    total = tot;
-    return wofs + x - v;
-}
-__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint64_t* sh, uint64_t& total)
-{
-    return block_excl_scan_u64_n<SCAN_BLOCK>(v, sh, total);
-}
-
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_reduce(const uint32_t* __restrict__ in, size_t n,
-                                                            uint64_t* __restrict__ part)
-{
-    __shared__ uint64_t sh[SCAN_BLOCK / 64];
-    const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++)
-        if (base + k < n) s += in[base + k];
-    uint64_t tot;
-    block_excl_scan_u64(s, sh, tot);
-    if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_part(uint64_t* __restrict__ part, int nb)
-{
-    __shared__ uint64_t sh[SCAN_BLOCK / 64];
-    uint64_t carry = 0;
-    for (int base = 0; base < nb; base += SCAN_BLOCK) {
-        const int i = base + threadIdx.x;
-        uint64_t v = i < nb ? part[i] : 0;
-        uint64_t tot;
-        uint64_t ex = block_excl_scan_u64(v, sh, tot);
-        __syncthreads();
-        if (i < nb) part[i] = carry + ex;
-        carry += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[nb] = carry;
-}
-
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_apply(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
-                                                           size_t n, const uint64_t* __restrict__ part, int exclusive)
-{
-    __shared__ uint64_t sh[SCAN_BLOCK / 64];
-    const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t v[SCAN_ITEMS];
-    uint64_t s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) {
-        v[k] = (base + k < n) ? in[base + k] : 0u;
-        s += v[k];
-    }
-    uint64_t tot;
-    uint64_t run = block_excl_scan_u64(s, sh, tot) + part[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) {
-        const uint64_t incl = run + v[k];
-        if (base + k < n) out[base + k] = (uint32_t)(exclusive ? run : incl);
-        run = incl;
-    }
-}
-
-hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t* part, size_t n, bool exclusive, hipStream_t st)
-{
-    const int nb = (int)((n + SCAN_TILE - 1) / SCAN_TILE);
-    if (nb > 0) k_scan_reduce<<<nb, SCAN_BLOCK, 0, st>>>(in, n, part);
-    k_scan_part<<<1, SCAN_BLOCK, 0, st>>>(part, nb);
-    if (nb > 0) k_scan_apply<<<nb, SCAN_BLOCK, 0, st>>>(in, out, n, part, exclusive ? 1 : 0);
-    return hipGetLastError();
-}
-
-// Publish the scan total: writes it as the closing entry of the tile-start
-// array (tile_end, may be null) and, packed with a sequence number, into a
-// coherent pinned host word the host spins on (lsr_api.hip bin_tiles, wait_published):
+// Publish the scan total of the global-atomic path (the privatised path's
+// count publishes its own): packed with a sequence number into a coherent
+// pinned host word the host spins on (lsr_api.hip bin_tiles, wait_published):
 // the host needs M to size the binning workspace, and polling one
 // PCIe-visible word avoids the staged D2H copy + stream-synchronise wake-up
 // latency in the middle of every forward.  Totals >= 2^32 - 1 saturate (the
 // host reports LSR_EOVERFLOW).
-__global__ void k_publish_total(const uint64_t* __restrict__ total, uint32_t* __restrict__ tile_end,
-                                uint64_t* host_slot, uint32_t seq, const uint32_t* __restrict__ cls_cnt)
+__global__ void k_publish_total(const uint64_t* __restrict__ total, uint64_t* host_slot, uint32_t seq)
 {
     const uint64_t m = *total;
     const uint32_t m32 = m >= 0xffffffffull ? 0xffffffffu : (uint32_t)m;
-    if (tile_end) *tile_end = m32;
-    if (cls_cnt) {
-        // per-class tile counts ride along in the same pinned line: the host
-        // launches exactly the sort classes that have work
-        uint32_t* h = (uint32_t*)(host_slot + 1);
-#pragma unroll
-        for (int k = 0; k < SORT_NCLS; k++) h[k] = cls_cnt[k];
-        __atomic_store_n(host_slot + LSR_CLS_SLOT, ((uint64_t)seq << 32) | m32, __ATOMIC_RELEASE);
-    }
     __atomic_store_n(host_slot, ((uint64_t)seq << 32) | m32, __ATOMIC_RELEASE);
 }
 
-hipError_t launch_publish_total(const uint64_t* total, uint32_t* tile_end, uint64_t* host_slot, uint32_t seq,
-                                const uint32_t* cls_cnt, hipStream_t st)
+hipError_t launch_publish_total(const uint64_t* total, const HostWord& hw, hipStream_t st)
 {
-    k_publish_total<<<1, 1, 0, st>>>(total, tile_end, host_slot, seq, cls_cnt);
+    k_publish_total<<<1, 1, 0, st>>>(total, hw.dev, hw.seq);
     return hipGetLastError();
-}
-
-// Sort size classes: 0 wave sort (n <= 512), 1..4 block merge sorts with
-// KPL = 4, 8, 16, 32 (n <= 256*KPL), 5 chunked LDS/global (n > 8192).  Empty
-// tiles are in no class.
-__device__ __forceinline__ int tile_class(int n)
-{
-    if (n <= 0) return -1;
-    if (n <= LSR_SORT_WAVE_MAX) return 0;
-    if (n <= 1024) return 1;
-    if (n <= 2048) return 2;
-    if (n <= 4096) return 3;
-    if (n <= 8192) return 4;
-    return 5;
-}
-
-// Wave-aggregated append of tile t (lanes with active) to its class list.
-// Every lane of the wave must call it.  One atomic instruction for the whole
-// wave: lane k adds the wave's class-k count to cls_cnt[k] (the classes'
-// adds are independent, so they share one round trip instead of one each).
-__device__ __forceinline__ void tile_class_append(bool active, int t, int n, int T, uint32_t* __restrict__ cls_cnt,
-                                                  uint32_t* __restrict__ cls_list)
-{
-    const int c = active ? tile_class(n) : -1;
-    const int lane = threadIdx.x & 63;
-    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    uint64_t m[SORT_NCLS];
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int k = 0; k < SORT_NCLS; k++) {
-        m[k] = __ballot(c == k);
-        cnt = lane == k ? (uint32_t)__popcll(m[k]) : cnt;
-    }
-    uint32_t base = 0;
-    if (cnt) base = atomicAdd(&cls_cnt[lane], cnt);
-    uint64_t mine = 0;
-#pragma unroll
-    for (int k = 0; k < SORT_NCLS; k++) mine = c == k ? m[k] : mine;
-    const uint32_t b = __shfl(base, c < 0 ? 0 : c, 64);
-    if (c >= 0) cls_list[(size_t)c * T + b + __popcll(mine & below)] = (uint32_t)t;
-}
-
-// Classification pass for the global-atomic binning path (the privatised path
-// classifies inside k_bin_table).  cls_cnt must be zero.
-__global__ void __launch_bounds__(256) k_tile_classify(int T, const uint32_t* __restrict__ tile_start,
-                                                       uint32_t* __restrict__ cls_cnt, uint32_t* __restrict__ cls_list)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const int n = t < T ? (int)(tile_start[t + 1] - tile_start[t]) : 0;
-    tile_class_append(t < T, t, n, T, cls_cnt, cls_list);
 }
 
 // ----------------------------------------------------- duplicate / scatter --
@@ -319,12 +154,7 @@ __device__ __forceinline__ int wave_spans_stage(WaveSpans& ws, int h, int bx0, i
     ws.me[lane] = sp.me;
     ws.box[lane] = bx0 | (bx1 << 16);
     ws.y0[lane] = y0;
-    int s = h;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(s, d, 64);
-        if (lane >= d) s += t;
-    }
+    const int s = wave_incl_scan(h);
     ws.rpre[lane] = s - h;
     if (lane == 63) ws.rpre[64] = s;
     wave_lds_fence();
@@ -357,12 +187,7 @@ __device__ __forceinline__ int wave_spans_round(WaveSpans& ws, int r0, int R, in
         wd = sx1 - sx0;
         packed = sx0 | (yr << 16) | (o << 24);
     }
-    int s = wd;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(s, d, 64);
-        if (lane >= d) s += t;
-    }
+    const int s = wave_incl_scan(wd);
     ws.epre[lane] = s - wd;
     if (lane == 63) ws.epre[64] = s;
     ws.ent[lane] = packed;
@@ -414,18 +239,14 @@ __global__ void __launch_bounds__(BB) k_bin_count(Cam c, int P, int chunk, int r
     __shared__ WaveSpans wss[BB / 64];
     __shared__ uint64_t s_tot;
     const int T = c.gx * c.gy;
-#if LSR_COUNT_XCD
-    // chunk-major, XCD-aware (as k_bin_scatter): a chunk's bands share an L2
+    // chunk-major, XCD-aware 1-D grid (as k_bin_scatter): a chunk's bands share
+    // an L2 (cfg5 bin_count 0.627 -> 0.604 ms against a chunk x band 2-D grid)
     const int o = xcd_remap(blockIdx.x, gridDim.x);
     const int blk = o / S;
     const Band bd(c, rows, o - blk * S);
-#else
-    const int blk = blockIdx.x;
-    const Band bd(c, rows, blockIdx.y);
-#endif
     // k_bin_table appends to the class counts and takes tickets after us
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < SORT_NCLS) cls_cnt[threadIdx.x] = 0;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) cls_cnt[LSR_TICKET_WORD] = 0;
+    if (blockIdx.x == 0 && threadIdx.x < SORT_NCLS) cls_cnt[threadIdx.x] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) cls_cnt[LSR_TICKET_WORD] = 0;
     for (int k = threadIdx.x; k < bd.nt; k += BB) hist[k] = 0;
     if (threadIdx.x == 0) s_tot = 0;
     __syncthreads();
@@ -461,12 +282,7 @@ __global__ void __launch_bounds__(BB) k_bin_count(Cam c, int P, int chunk, int r
         uint32_t carry = 0;
         for (int x0 = 0; x0 < c.gx; x0 += 64) {
             const int x = x0 + lane;
-            uint32_t v = x < c.gx ? hist[r * c.gx + x] : 0u;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = __shfl_up(v, d, 64);
-                if (lane >= d) v += t;
-            }
+            const uint32_t v = wave_incl_scan(x < c.gx ? hist[r * c.gx + x] : 0u);
             if (x < c.gx) {
                 row[r * c.gx + x] = carry + v;
                 mine += carry + v;
@@ -488,7 +304,7 @@ __global__ void __launch_bounds__(BB) k_bin_count(Cam c, int P, int chunk, int r
         const uint64_t add = s_tot + (1ull << 44);
         const uint64_t prev = __hip_atomic_fetch_add((uint64_t*)(cls_cnt + LSR_COUNT_WORD), add, __ATOMIC_RELAXED,
                                                      __HIP_MEMORY_SCOPE_AGENT);
-        if ((prev >> 44) == (uint64_t)gridDim.x * gridDim.y - 1) {
+        if ((prev >> 44) == (uint64_t)gridDim.x - 1) {
             const uint64_t m = (prev + add) & ((1ull << 44) - 1);
             const uint32_t m32 = m >= 0xffffffffull ? 0xffffffffu : (uint32_t)m;
             __hip_atomic_store(host_slot, ((uint64_t)seq << 32) | m32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -518,7 +334,7 @@ struct BinPublish {
     uint64_t* gpart;      // per tile group: total, then (last block) exclusive base; [G] = M
     uint32_t* ticket;     // arrival counter, zero on entry
     uint32_t* tile_end;   // tile_start + T
-    uint64_t* host_slot;  // pinned host word LSR_CLS_SLOT (the class counts are words 1..3)
+    uint64_t* host_slot;  // pinned host word LSR_CLS_SLOT (the class counts: u32 words 2 .. 1 + SORT_NCLS of the line)
     uint32_t seq;
 };
 __device__ __forceinline__ uint32_t u4_get(const uint4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
@@ -655,6 +471,8 @@ __global__ void __launch_bounds__(256) k_tile_start_apply(int T, const uint32_t*
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     const uint32_t v = t < T ? tile_cnt[t] : 0u;
+    // (wave_incl_scan written out: through the helper this kernel compiles to
+    // other code, and it is held to the code it had, tools/kernel_diff.py)
     uint32_t x = v;
     const int l = threadIdx.x & 63;
 #pragma unroll
@@ -775,9 +593,12 @@ static int bin_band_rows(const Cam& c, int P)
 int scatter_merge(int P) { return LSR_SCATTER_MERGE > 0 ? LSR_SCATTER_MERGE : (P >= (4 << 20) ? 4 : 1); }
 int bin_scatter_rows(const Cam& c)
 {
-    if (LSR_SCATTER_ROWS > 0) return std::max(1, std::min(c.gy, LSR_SCATTER_ROWS));
-    return std::max(1, std::min(c.gy, LSR_SCATTER_LDS / (4 * c.gx)));
+    const int fit = LSR_SCATTER_LDS / (4 * c.gx);
+    return std::max(1, std::min(c.gy, LSR_SCATTER_ROWS > 0 ? std::min(LSR_SCATTER_ROWS, fit) : fit));
 }
+// the bands' dynamic LDS (bin_band_rows, bin_scatter_rows) stays within the
+// 64 KB a launch may ask for without raising the kernel's limit
+static_assert(2 * LSR_BAND_LDS <= 65536 && LSR_SCATTER_LDS <= 65536, "count / scatter bands must fit 64 KB of dynamic LDS");
 
 // Threads per (chunk, band) scatter block (and the chunk granule): 16 waves
 // below 4M Gaussians, 8 waves from 4M up (16 measured slower at cfg5: scatter
@@ -805,554 +626,51 @@ int bin_blocks(int P, const Cam& c, int& chunk)
 // table of moderate size.
 bool bin_privatised_ok(const Cam& c) { return (size_t)c.gx * 4 <= LSR_BAND_LDS && (size_t)c.gx * c.gy <= (1u << 20); }
 
-hipError_t launch_bin_count(const Cam& c, int P, int chunk, int B, const uint8_t* geom, const int32_t* radii,
-                            uint32_t* table, uint32_t* tile_cnt, uint32_t* tile_start, uint64_t* tpart,
-                            uint32_t* cls_cnt, uint32_t* cls_list, uint64_t* host_slot, uint32_t seq, hipStream_t st)
+// The launchers below run on the privatised path only: P > 0 and ws.B >= 1
+// chunks (lsr_api.hip BinShape).
+hipError_t launch_bin_count(const Cam& c, int P, const uint8_t* geom, const int32_t* radii, const BinWs& ws,
+                            const HostWord& hw, hipStream_t st)
 {
-    const int T = c.gx * c.gy;
+    const int T = c.gx * c.gy, B = ws.B;
     const int rows = bin_band_rows(c, P);
     const int S = (c.gy + rows - 1) / rows;
-    const dim3 grid(LSR_COUNT_XCD ? B * S : B, LSR_COUNT_XCD ? 1 : S);
     const size_t lds = (size_t)rows * c.gx * 4;
-    if (lds > 65536) {
-        (void)hipFuncSetAttribute((const void*)k_bin_count<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)k_bin_scatter<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)k_bin_scatter<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    if (B > 0) {
-        // 8-wave count blocks at every size (r05, with the 68-row bands and the
-        // colour pass beside it: cfg3 bin_count 0.104 -> 0.077 ms, step -1.3 / -1.7 %
-        // in both A/B orders, profiles/r05s3_ab_tune{2,3}_cfg3.txt); the scatter keeps
-        // bin_block's 16 waves below 4M
-        if ((size_t)grid.x * grid.y >= (1u << 20)) return hipErrorInvalidValue;   // arrivals field (bits 44+)
-        k_bin_count<512><<<grid, 512, lds, st>>>(c, P, chunk, rows, S, geom, radii, table, cls_cnt, host_slot, seq);
-        BinPublish pb{tpart, cls_cnt + LSR_TICKET_WORD, tile_start + T, host_slot + LSR_CLS_SLOT, seq};
-        const int G = (T + TBL_TILES - 1) / TBL_TILES, Tp = table_stride(T);
-        if (B <= 16 * TBL_RPT)
-            k_bin_table<16><<<G, 256, 0, st>>>(T, Tp, B, table, tile_cnt, cls_cnt, cls_list, pb);
-        else if (B <= 32 * TBL_RPT)
-            k_bin_table<32><<<G, 512, 0, st>>>(T, Tp, B, table, tile_cnt, cls_cnt, cls_list, pb);
-        else if (B <= 64 * TBL_RPT)
-            k_bin_table<64><<<G, 1024, 0, st>>>(T, Tp, B, table, tile_cnt, cls_cnt, cls_list, pb);
-        else
-            return hipErrorInvalidValue;   // bin_blocks keeps B <= 2 * LSR_BIN_TARGET
-    } else {
-        (void)hipMemsetAsync(tile_cnt, 0, (size_t)T * 4, st);
-        (void)hipMemsetAsync(cls_cnt, 0, SORT_NCLS * 4, st);
-        (void)launch_scan_u32(tile_cnt, tile_start, tpart, (size_t)T, true, st);
-        (void)launch_publish_total(tpart + (scan_partials((size_t)T) - 1), tile_start + T, host_slot, seq, cls_cnt, st);
-    }
+    // 8-wave count blocks at every size (r05, with the 68-row bands and the
+    // colour pass beside it: cfg3 bin_count 0.104 -> 0.077 ms, step -1.3 / -1.7 %
+    // in both A/B orders, profiles/r05s3_ab_tune{2,3}_cfg3.txt); the scatter keeps
+    // bin_block's 16 waves below 4M
+    if ((size_t)B * S >= (1u << 20)) return hipErrorInvalidValue;   // arrivals field (bits 44+)
+    k_bin_count<512><<<B * S, 512, lds, st>>>(c, P, ws.chunk, rows, S, geom, radii, ws.table, ws.cls_cnt, hw.dev, hw.seq);
+    BinPublish pb{ws.tpart, ws.cls_cnt + LSR_TICKET_WORD, ws.tile_start + T, hw.dev + LSR_CLS_SLOT, hw.seq};
+    const int G = (T + TBL_TILES - 1) / TBL_TILES, Tp = table_stride(T);
+    if (B <= 16 * TBL_RPT)
+        k_bin_table<16><<<G, 256, 0, st>>>(T, Tp, B, ws.table, ws.tile_cnt, ws.cls_cnt, ws.cls_list, pb);
+    else if (B <= 32 * TBL_RPT)
+        k_bin_table<32><<<G, 512, 0, st>>>(T, Tp, B, ws.table, ws.tile_cnt, ws.cls_cnt, ws.cls_list, pb);
+    else if (B <= 64 * TBL_RPT)
+        k_bin_table<64><<<G, 1024, 0, st>>>(T, Tp, B, ws.table, ws.tile_cnt, ws.cls_cnt, ws.cls_list, pb);
+    else
+        return hipErrorInvalidValue;   // bin_blocks keeps B <= 2 * LSR_BIN_TARGET
     return hipGetLastError();
 }
 
-hipError_t launch_tile_start_apply(int T, int B, const uint32_t* tile_cnt, const uint64_t* tpart, uint32_t* tile_start,
-                                   hipStream_t st)
+hipError_t launch_tile_start_apply(int T, const BinWs& ws, hipStream_t st)
 {
-    if (B > 0 && T > 0) k_tile_start_apply<<<(T + 255) / 256, 256, 0, st>>>(T, tile_cnt, tpart, tile_start);
+    if (T > 0) k_tile_start_apply<<<(T + 255) / 256, 256, 0, st>>>(T, ws.tile_cnt, ws.tpart, ws.tile_start);
     return hipGetLastError();
 }
 
-hipError_t launch_bin_scatter(const Cam& c, int P, int chunk, int B, const uint8_t* geom, const int32_t* radii,
-                              const uint32_t* table, const uint32_t* tile_start, uint64_t* keys, hipStream_t st)
+hipError_t launch_bin_scatter(const Cam& c, int P, const uint8_t* geom, const int32_t* radii, const BinWs& ws,
+                              uint64_t* keys, hipStream_t st)
 {
     const int rows = bin_scatter_rows(c);
     const int S = (c.gy + rows - 1) / rows;
     const size_t lds = (size_t)rows * c.gx * 4;
-    if (lds > 65536) {
-        (void)hipFuncSetAttribute((const void*)k_bin_scatter<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)k_bin_scatter<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    const int km = scatter_merge(P), Bs = (B + km - 1) / km;
-    if (B > 0 && bin_block(P) == 1024)
-        k_bin_scatter<1024><<<Bs * S, 1024, lds, st>>>(c, P, chunk, km, rows, S, geom, radii, table, tile_start, keys);
-    else if (B > 0)
-        k_bin_scatter<512><<<Bs * S, 512, lds, st>>>(c, P, chunk, km, rows, S, geom, radii, table, tile_start, keys);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------ tile sort ---
-// Ascending flip-bitonic network over n keys with virtual +inf padding to the
-// next power of two: every compare-exchange puts the minimum at the lower
-// index, so pairs whose upper index is >= n are no-ops and are skipped.
-#define SORT_BLOCK 256
-#define SORT_CHUNK 4096
-
-__device__ __forceinline__ void ce(uint64_t* a, int i, int l)
-{
-    uint64_t x = a[i], y = a[l];
-    if (x > y) { a[i] = y; a[l] = x; }
-}
-
-// Full network for k = 2..kmax over a[0, n) (n <= kmax), in LDS.
-__device__ void bitonic_lds(uint64_t* a, int n, int kmax)
-{
-    for (int k = 2; k <= kmax; k <<= 1) {
-        const int hk = k >> 1;
-        for (int p = threadIdx.x; p < kmax / 2; p += SORT_BLOCK) {
-            const int blk = p / hk, off = p % hk;
-            const int i = blk * k + off, l = blk * k + k - 1 - off;
-            if (l < n) ce(a, i, l);
-        }
-        __syncthreads();
-        for (int j = k >> 2; j >= 1; j >>= 1) {
-            for (int p = threadIdx.x; p < kmax / 2; p += SORT_BLOCK) {
-                const int i = (p / j) * 2 * j + (p % j), l = i + j;
-                if (l < n) ce(a, i, l);
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// Half-cleaner steps j = jmax..1 over a[0, n) in LDS (n <= chunk).
-__device__ void halfclean_lds(uint64_t* a, int n, int chunk, int jmax)
-{
-    for (int j = jmax; j >= 1; j >>= 1) {
-        for (int p = threadIdx.x; p < chunk / 2; p += SORT_BLOCK) {
-            const int i = (p / j) * 2 * j + (p % j), l = i + j;
-            if (l < n) ce(a, i, l);
-        }
-        __syncthreads();
-    }
-}
-
-__device__ __forceinline__ int next_pow2(int n)
-{
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-// Tiles of class 5 (n > 8192): one workgroup per tile (grid-stride over the
-// class list), chunk-local bitonic stages in LDS, cross-chunk stages in
-// global memory.
-__device__ void tile_sort_big(int t, const uint32_t* __restrict__ tile_start, uint64_t* __restrict__ keys,
-                              uint32_t* __restrict__ point_list, uint64_t* buf)
-{
-    const uint32_t s0 = tile_start[t], s1 = tile_start[t + 1];
-    const int n = (int)(s1 - s0);
-    uint64_t* g = keys + s0;
-    if (n <= SORT_CHUNK) {
-        for (int k = threadIdx.x; k < n; k += SORT_BLOCK) buf[k] = g[k];
-        __syncthreads();
-        bitonic_lds(buf, n, next_pow2(n));
-        for (int k = threadIdx.x; k < n; k += SORT_BLOCK) point_list[s0 + k] = (uint32_t)buf[k];
-        __syncthreads();
-        return;
-    }
-    // Large tile: chunk-local stages in LDS, cross-chunk stages in global
-    // memory (one workgroup owns the tile; __syncthreads orders its passes).
-    const int n2 = next_pow2(n);
-    const int nch = (n + SORT_CHUNK - 1) / SORT_CHUNK;
-    for (int ch = 0; ch < nch; ch++) {
-        const int cb = ch * SORT_CHUNK, cn = min(SORT_CHUNK, n - cb);
-        for (int k = threadIdx.x; k < cn; k += SORT_BLOCK) buf[k] = g[cb + k];
-        __syncthreads();
-        bitonic_lds(buf, cn, SORT_CHUNK);
-        for (int k = threadIdx.x; k < cn; k += SORT_BLOCK) g[cb + k] = buf[k];
-        __syncthreads();
-    }
-    for (int k = 2 * SORT_CHUNK; k <= n2; k <<= 1) {
-        const int hk = k >> 1;
-        for (int p = threadIdx.x; p < n2 / 2; p += SORT_BLOCK) {
-            const int blk = p / hk, off = p % hk;
-            const int i = blk * k + off, l = blk * k + k - 1 - off;
-            if (l < n) ce(g, i, l);
-        }
-        __syncthreads();
-        for (int j = k >> 2; j >= SORT_CHUNK; j >>= 1) {
-            for (int p = threadIdx.x; p < n2 / 2; p += SORT_BLOCK) {
-                const int i = (p / j) * 2 * j + (p % j), l = i + j;
-                if (l < n) ce(g, i, l);
-            }
-            __syncthreads();
-        }
-        for (int ch = 0; ch < nch; ch++) {
-            const int cb = ch * SORT_CHUNK, cn = min(SORT_CHUNK, n - cb);
-            for (int q = threadIdx.x; q < cn; q += SORT_BLOCK) buf[q] = g[cb + q];
-            __syncthreads();
-            halfclean_lds(buf, cn, SORT_CHUNK, SORT_CHUNK / 2);
-            for (int q = threadIdx.x; q < cn; q += SORT_BLOCK) g[cb + q] = buf[q];
-            __syncthreads();
-        }
-    }
-    for (int k = threadIdx.x; k < n; k += SORT_BLOCK) point_list[s0 + k] = (uint32_t)g[k];
-    __syncthreads();
-}
-
-__global__ void __launch_bounds__(SORT_BLOCK) k_tile_sort_big(int T, const uint32_t* __restrict__ tile_start,
-                                                              uint64_t* __restrict__ keys,
-                                                              uint32_t* __restrict__ point_list,
-                                                              const uint32_t* __restrict__ cls_cnt,
-                                                              const uint32_t* __restrict__ cls_list)
-{
-    __shared__ uint64_t buf[SORT_CHUNK];
-    const uint32_t cnt = cls_cnt[5];
-    for (uint32_t i = blockIdx.x; i < cnt; i += gridDim.x)
-        tile_sort_big((int)cls_list[(size_t)5 * T + i], tile_start, keys, point_list, buf);
-}
-
-// Wave-level register bitonic sort of a full run of 64*KPL keys (the 4-wave
-// block sort's per-wave runs): lane l holds elements [l*KPL, l*KPL + KPL)
-// (padding = UINT64_MAX).  Steps whose partner distance j < KPL run inside the
-// lane's registers; the others pair lane l with lane l ^ (j / KPL) through
-// lane exchanges.  No LDS, no barriers.  (The one-wave tile sort has its own
-// network, sized by the key count: wave_sort_tile below.)
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m)
-{
-    const uint32_t lo = __shfl_xor((uint32_t)v, m, 64);
-    const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-#ifndef LSR_SORT_XBATCH
-#define LSR_SORT_XBATCH 1
-#endif
-// xor_lane_u32 (the register-path lane exchange) lives in lsr_device.h, where
-// tests/micro/micro_checks.hip checks it against __shfl_xor on the GPU.
-template <int M>
-__device__ __forceinline__ uint64_t xor_lane_u64(uint64_t v)
-{
-#if LSR_SORT_DPP
-    const uint32_t lo = xor_lane_u32<M>((uint32_t)v);
-    const uint32_t hi = xor_lane_u32<M>((uint32_t)(v >> 32));
-    return ((uint64_t)hi << 32) | lo;
-#else
-    return shfl_xor_u64(v, M);
-#endif
-}
-
-template <int KPL, int K, int J>
-__device__ __forceinline__ void wave_sort_xstep(uint64_t (&v)[KPL])
-{
-    constexpr int M = J / KPL;
-    const int lane = threadIdx.x & 63;
-    // K >= 2J >= 2 KPL: the direction bit of element lane*KPL + r is the
-    // lane's alone, so one flag serves all KPL elements
-    const bool take_min = ((lane & M) == 0) == (((lane * KPL) & K) == 0);
-#if LSR_SORT_XBATCH
-    // every partner first, then every select: the lane exchanges (DPP /
-    // permlane) read registers the previous step wrote long before, so no
-    // hazard wait states sit between a select and the exchange that needs it
-    uint64_t o[KPL];
-#pragma unroll
-    for (int r = 0; r < KPL; r++) o[r] = xor_lane_u64<M>(v[r]);
-#pragma unroll
-    for (int r = 0; r < KPL; r++) v[r] = ((v[r] < o[r]) == take_min) ? v[r] : o[r];
-#else
-#pragma unroll
-    for (int r = 0; r < KPL; r++) {
-        const uint64_t o = xor_lane_u64<M>(v[r]);
-        v[r] = ((v[r] < o) == take_min) ? v[r] : o;   // keep own value iff it is the wanted one
-    }
-#endif
-}
-
-template <int KPL, int K, int J>
-__device__ __forceinline__ void wave_sort_steps(uint64_t (&v)[KPL])
-{
-    if constexpr (J >= 1) {
-        if constexpr (J < KPL) {
-            const int lane = threadIdx.x & 63;
-            // direction of element lane*KPL + r: from r alone while K < KPL
-            // (compile time), from the lane alone once K >= KPL (r < KPL <= K
-            // never reaches bit K): one compare + one mask XOR per pair
-            const bool desc_lane = ((lane * KPL) & K) != 0;
-#pragma unroll
-            for (int r = 0; r < KPL; r++) {
-                if (r & J) continue;
-                const uint64_t a = v[r], b = v[r | J];
-                bool sw;
-                if constexpr (K < KPL) sw = (r & K) ? (a < b) : (a > b);
-                else sw = (a > b) != desc_lane;
-                v[r] = sw ? b : a;
-                v[r | J] = sw ? a : b;
-            }
-        } else {
-            wave_sort_xstep<KPL, K, J>(v);
-        }
-        wave_sort_steps<KPL, K, J / 2>(v);
-    }
-}
-
-template <int KPL, int K>
-__device__ __forceinline__ void wave_sort_stages(uint64_t (&v)[KPL])
-{
-    if constexpr (K <= 64 * KPL) {
-        wave_sort_steps<KPL, K, K / 2>(v);
-        wave_sort_stages<KPL, 2 * K>(v);
-    }
-}
-
-// The one-wave tile sort (class 0) sizes its network by the tile's key count:
-// KPL = ceil(n / 64) keys per lane, not a power of two (the power-of-two network
-// it replaces ran 1024 slots for cfg3's 487..715 keys).  Lane l holds elements
-// [l*KPL, l*KPL + KPL), +inf from n up.  A merge sort whose runs are lanes:
-//  - every lane sorts its KPL registers (Batcher's odd-even merge sort, which
-//    exists for every length: 32 compare-exchanges at KPL = 10, 63 at 16);
-//  - for m = 2, 4 .. 64 lanes: the flip pairs element (l, r) with
-//    (l ^ (m - 1), KPL - 1 - r), the minimum to the lower lane, which leaves
-//    both halves bitonic and the lower one below the upper; half-cleaners at
-//    lane distances m/4 .. 1 (every register against the same register of
-//    lane l ^ d) then leave every lane a bitonic KPL keys that lie between
-//    its neighbours', and the lane's own sort finishes the stage.
-// The flip and the half-cleaner hold for runs of any equal length, so nothing
-// is padded to a power of two.  21 lane-exchange steps in all (the log2 m of
-// every stage), each over KPL registers, with every partner fetched before
-// every select as in wave_sort_xstep.  Same keys, total order: the output is
-// the full network's.
-template <int KPL>
-__device__ __forceinline__ void lane_sort_regs(uint64_t (&v)[KPL])
-{
-    // odd-even merge sort over v[0, KPL), every index a compile-time constant
-#pragma unroll
-    for (int p = 1; p < KPL; p *= 2) {
-#pragma unroll
-        for (int k = p; k >= 1; k /= 2) {
-#pragma unroll
-            for (int j = k % p; j + k < KPL; j += 2 * k) {
-#pragma unroll
-                for (int i = 0; i < k; i++) {
-                    const int a = i + j, b = i + j + k;
-                    if (b >= KPL || a / (2 * p) != b / (2 * p)) continue;
-                    const uint64_t x = v[a], y = v[b];
-                    const bool sw = x > y;
-                    v[a] = sw ? y : x;
-                    v[b] = sw ? x : y;
-                }
-            }
-        }
-    }
-}
-
-// One lane-exchange step: register r against register (FLIP ? KPL - 1 - r : r)
-// of lane l ^ M; the lane whose bit LOW is clear keeps the minimum.
-template <int KPL, int M, int LOW, bool FLIP>
-__device__ __forceinline__ void wsort_xstep(uint64_t (&v)[KPL])
-{
-    const int lane = threadIdx.x & 63;
-    const bool take_min = (lane & LOW) == 0;
-    uint64_t o[KPL];
-#pragma unroll
-    for (int r = 0; r < KPL; r++) o[r] = xor_lane_u64<M>(v[FLIP ? KPL - 1 - r : r]);
-#pragma unroll
-    for (int r = 0; r < KPL; r++) v[r] = ((v[r] < o[r]) == take_min) ? v[r] : o[r];
-}
-
-template <int KPL, int D>
-__device__ __forceinline__ void wsort_halfclean(uint64_t (&v)[KPL])
-{
-    if constexpr (D >= 1) {
-        wsort_xstep<KPL, D, D, false>(v);
-        wsort_halfclean<KPL, D / 2>(v);
-    }
-}
-
-template <int KPL, int M>
-__device__ __forceinline__ void wsort_merge_lanes(uint64_t (&v)[KPL])
-{
-    if constexpr (M <= 64) {
-        wsort_xstep<KPL, M - 1, M / 2, true>(v);
-        wsort_halfclean<KPL, M / 4>(v);
-        lane_sort_regs<KPL>(v);
-        wsort_merge_lanes<KPL, 2 * M>(v);
-    }
-}
-
-// n <= 64 KPL keys of one tile, sorted by one wave.
-template <int KPL>
-__device__ __forceinline__ void wave_sort_tile(const uint64_t* __restrict__ g, uint32_t* __restrict__ out, int n)
-{
-    const int lane = threadIdx.x & 63;
-    uint64_t v[KPL];
-#pragma unroll
-    for (int r = 0; r < KPL; r++) {
-        const int e = lane * KPL + r;
-        v[r] = e < n ? g[e] : ~0ull;
-    }
-    lane_sort_regs<KPL>(v);
-    wsort_merge_lanes<KPL, 2>(v);
-#pragma unroll
-    for (int r = 0; r < KPL; r++) {
-        const int e = lane * KPL + r;
-        if (e < n) out[e] = (uint32_t)v[r];
-    }
-}
-
-// LDS slot of logical element e of a block sort: one u64 of padding every 16
-// keys, so the lane-major run reads (lane stride KPL*8 bytes) spread over
-// the banks instead of piling onto a few.
-__device__ __forceinline__ int lpad(int e) { return e + (e >> 4); }
-
-// Merge-path co-rank: how many of the first d outputs of merge(A, B) come
-// from A, A = lds[a0, a0+na), B = lds[b0, b0+nb) (logical indices; keys are
-// unique, so ties never occur).
-__device__ __forceinline__ int merge_corank(const uint64_t* lds, int a0, int na, int b0, int nb, int d)
-{
-    int lo = max(0, d - nb), hi = min(d, na);
-    while (lo < hi) {
-        const int m = (lo + hi) >> 1;
-        if (lds[lpad(a0 + m)] < lds[lpad(b0 + d - 1 - m)]) lo = m + 1;
-        else hi = m;
-    }
-    return lo;
-}
-
-// KPL consecutive outputs of merge(A, B) starting at output d, into v.
-template <int KPL>
-__device__ __forceinline__ void merge_run(const uint64_t* lds, int a0, int na, int b0, int nb, int d,
-                                          uint64_t (&v)[KPL])
-{
-    int i = merge_corank(lds, a0, na, b0, nb, d), j = d - i;
-    uint64_t a = i < na ? lds[lpad(a0 + i)] : ~0ull, b = j < nb ? lds[lpad(b0 + j)] : ~0ull;
-#pragma unroll
-    for (int k = 0; k < KPL; k++) {
-        const bool ta = a < b;
-        v[k] = ta ? a : b;
-        i += ta ? 1 : 0;
-        j += ta ? 0 : 1;
-        const bool ok = ta ? (i < na) : (j < nb);
-        const uint64_t nx = ok ? lds[lpad(ta ? a0 + i : b0 + j)] : ~0ull;
-        a = ta ? nx : a;
-        b = ta ? b : nx;
-    }
-}
-
-// One 4-wave workgroup per tile of 128*KPL < n <= 256*KPL keys.  The bucket
-// is staged into LDS with coalesced loads (+inf padding), each wave sorts a
-// 64*KPL run in registers (the wave bitonic network above), two merge-path
-// rounds (every thread producing KPL consecutive outputs after a binary
-// co-rank search) finish the order, and the ids leave through LDS with
-// coalesced stores.
-template <int KPL>
-__device__ __forceinline__ void block_sort_tile(const uint64_t* __restrict__ g, uint32_t* __restrict__ out, int n,
-                                                uint64_t* lds)
-{
-    constexpr int R = 64 * KPL;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    // batches of 8 loads in flight per thread (a full unroll would hold all
-    // 4*KPL keys in VGPRs and collapse occupancy)
-#pragma unroll 1
-    for (int k0 = 0; k0 < 4 * KPL; k0 += 8) {
-        uint64_t x[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int e = (k0 + k) * 256 + tid;
-            x[k] = e < n ? g[e] : ~0ull;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) lds[lpad((k0 + k) * 256 + tid)] = x[k];
-    }
-    __syncthreads();
-    uint64_t v[KPL];
-#pragma unroll
-    for (int r = 0; r < KPL; r++) v[r] = lds[lpad(w * R + lane * KPL + r)];
-    wave_sort_stages<KPL, 2>(v);
-#pragma unroll
-    for (int r = 0; r < KPL; r++) lds[lpad(w * R + lane * KPL + r)] = v[r];
-    __syncthreads();
-    {
-        const int p0 = (tid >> 7) * 2 * R, d = (tid & 127) * KPL;
-        merge_run<KPL>(lds, p0, R, p0 + R, R, d, v);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < KPL; k++) lds[lpad(p0 + d + k)] = v[k];
-    }
-    __syncthreads();
-    const int d = tid * KPL;
-    merge_run<KPL>(lds, 0, 2 * R, 2 * R, 2 * R, d, v);
-    __syncthreads();
-    uint32_t* l32 = (uint32_t*)lds;
-#pragma unroll
-    for (int k = 0; k < KPL; k++) l32[d + k + ((d + k) >> 5)] = (uint32_t)v[k];
-    __syncthreads();
-#pragma unroll 8
-    for (int e = tid; e < n; e += 256) out[e] = l32[e + (e >> 5)];
-    __syncthreads();
-}
-
-// Class c = 1..4 (KPL = 4 << (c - 1)): one workgroup per listed tile.
-template <int KPL>
-__global__ void __launch_bounds__(256) k_tile_sort_blk(int T, const uint32_t* __restrict__ tile_start,
-                                                       const uint64_t* __restrict__ keys,
-                                                       uint32_t* __restrict__ point_list,
-                                                       const uint32_t* __restrict__ cls_cnt,
-                                                       const uint32_t* __restrict__ cls_list, int cls)
-{
-    __shared__ uint64_t lds[(4 * 64 * KPL) * 17 / 16];
-    const uint32_t cnt = cls_cnt[cls];
-    for (uint32_t i = blockIdx.x; i < cnt; i += gridDim.x) {
-        const int t = (int)cls_list[(size_t)cls * T + i];
-        const uint32_t s0 = tile_start[t];
-        block_sort_tile<KPL>(keys + s0, point_list + s0, (int)(tile_start[t + 1] - s0), lds);
-    }
-}
-
-// Class 0 (n <= LSR_SORT_WAVE_MAX): one wave per listed tile, four per workgroup.
-// (capped at the 128 VGPRs of 4 waves per SIMD, the occupancy of the power-of-two
-// network it replaces: uncapped the scheduler takes 136)
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
-k_tile_sort_wave(int T, const uint32_t* __restrict__ tile_start,
-                                                        const uint64_t* __restrict__ keys,
-                                                        uint32_t* __restrict__ point_list,
-                                                        const uint32_t* __restrict__ cls_cnt,
-                                                        const uint32_t* __restrict__ cls_list)
-{
-    const uint32_t cnt = cls_cnt[0];
-    for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < cnt; i += gridDim.x * 4) {
-        const int t = (int)cls_list[i];
-        const uint32_t s0 = tile_start[t];
-        const int n = (int)(tile_start[t + 1] - s0);
-        const uint64_t* g = keys + s0;
-        uint32_t* o = point_list + s0;
-        // keys per lane: every count up to 4, even counts above (the odd ones from 5
-        // up spill at the 128 VGPRs of 4 waves per SIMD)
-        if (n == 1) {
-            if ((threadIdx.x & 63) == 0) o[0] = (uint32_t)g[0];
-            continue;
-        }
-        int kpl = (n + 63) >> 6;
-        if (kpl > 4) kpl = (kpl + 1) & ~1;
-        switch (kpl) {
-        case 1: wave_sort_tile<1>(g, o, n); break;
-        case 2: wave_sort_tile<2>(g, o, n); break;
-        case 3: wave_sort_tile<3>(g, o, n); break;
-        case 4: wave_sort_tile<4>(g, o, n); break;
-        case 6: wave_sort_tile<6>(g, o, n); break;
-        case 8: wave_sort_tile<8>(g, o, n); break;
-        case 10: wave_sort_tile<10>(g, o, n); break;
-        case 12: wave_sort_tile<12>(g, o, n); break;
-        case 14: wave_sort_tile<14>(g, o, n); break;
-        default: wave_sort_tile<16>(g, o, n); break;
-        }
-    }
-}
-
-// host_cnt: the per-class tile counts when the host already has them (the
-// privatised binning path publishes them with M); null = unknown, the lists
-// are built here and every class runs a persistent grid.
-hipError_t launch_tile_sort(int T, const uint32_t* tile_start, uint64_t* keys, uint32_t* point_list,
-                            uint32_t* cls_cnt, uint32_t* cls_list, const uint32_t* host_cnt, hipStream_t st)
-{
-    if (T == 0) return hipSuccess;
-    uint32_t cnt[SORT_NCLS];
-    if (host_cnt) {
-        for (int k = 0; k < SORT_NCLS; k++) cnt[k] = host_cnt[k];
-    } else {
-        (void)hipMemsetAsync(cls_cnt, 0, SORT_NCLS * 4, st);
-        k_tile_classify<<<(T + 255) / 256, 256, 0, st>>>(T, tile_start, cls_cnt, cls_list);
-        // persistent grids: enough workgroups to fill the chip, or the tiles
-        const uint32_t fill[SORT_NCLS] = {256 * 8, 256 * 8, 256 * 8, 256 * 4, 256 * 2, 256 * 2};
-        for (int k = 0; k < SORT_NCLS; k++) cnt[k] = std::min<uint32_t>((uint32_t)T, fill[k] * (k == 0 ? 4 : 1));
-    }
-    const uint32_t* cc = cls_cnt;
-    const uint32_t* cl = cls_list;
-    if (cnt[0]) k_tile_sort_wave<<<(cnt[0] + 3) / 4, 256, 0, st>>>(T, tile_start, keys, point_list, cc, cl);
-    if (cnt[1]) k_tile_sort_blk<4><<<cnt[1], 256, 0, st>>>(T, tile_start, keys, point_list, cc, cl, 1);
-    if (cnt[2]) k_tile_sort_blk<8><<<cnt[2], 256, 0, st>>>(T, tile_start, keys, point_list, cc, cl, 2);
-    if (cnt[3]) k_tile_sort_blk<16><<<cnt[3], 256, 0, st>>>(T, tile_start, keys, point_list, cc, cl, 3);
-    if (cnt[4]) k_tile_sort_blk<32><<<cnt[4], 256, 0, st>>>(T, tile_start, keys, point_list, cc, cl, 4);
-    if (cnt[5]) k_tile_sort_big<<<cnt[5], SORT_BLOCK, 0, st>>>(T, tile_start, keys, point_list, cc, cl);
+    const int km = scatter_merge(P), Bs = (ws.B + km - 1) / km;
+    if (bin_block(P) == 1024)
+        k_bin_scatter<1024><<<Bs * S, 1024, lds, st>>>(c, P, ws.chunk, km, rows, S, geom, radii, ws.table, ws.tile_start, keys);
+    else
+        k_bin_scatter<512><<<Bs * S, 512, lds, st>>>(c, P, ws.chunk, km, rows, S, geom, radii, ws.table, ws.tile_start, keys);
     return hipGetLastError();
 }
 

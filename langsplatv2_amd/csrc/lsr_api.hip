@@ -197,9 +197,10 @@ struct ColourJoin {
 
 // ------------------------------------------------- host-visible scan total
 // One coherent pinned line per host thread: word 0 receives (seq << 32 | M)
-// from k_bin_count (k_publish_total on the global-atomic path), words 1..3 the
-// tile-sort class counts and word LSR_CLS_SLOT (seq << 32 | M) once those are
-// out (k_bin_table); the host spins until a word's sequence matches.
+// from k_bin_count (k_publish_total on the global-atomic path), the u32 words
+// 2 .. 1 + SORT_NCLS (inside u64 words 1..3) the tile-sort class counts and
+// word LSR_CLS_SLOT (seq << 32 | M) once those are out (k_bin_table); the host
+// spins until a word's sequence matches.
 struct HostSlot {
     uint64_t* word = nullptr;   // host view
     uint64_t* dev = nullptr;    // device view of the same word
@@ -339,27 +340,24 @@ int bin_tiles(const lsr_settings* s, const Cam& c, int P, const BinShape& bs, ui
     const int T = c.gx * c.gy;
     const GeomLayout GL = geom_layout((size_t)P);
     const ImageLayout IL = image_layout((size_t)c.W * c.H, (size_t)T);
-    uint32_t* table = (uint32_t*)(img + IL.total);
-    uint32_t* tile_cnt = (uint32_t*)(img + IL.tile_cnt);
-    uint32_t* tile_start = (uint32_t*)(img + IL.tile_start);
-    uint64_t* tpart = (uint64_t*)(img + IL.tile_part);
+    const BinWs ws{bs.chunk, bs.B, (uint32_t*)(img + IL.total), (uint32_t*)(img + IL.tile_cnt),
+                   (uint32_t*)(img + IL.tile_start), (uint64_t*)(img + IL.tile_part), (uint32_t*)(img + IL.cls_cnt),
+                   (uint32_t*)(img + IL.cls_list)};
     const size_t tnb = scan_partials((size_t)T) - 1;
-    uint32_t* cls_cnt = (uint32_t*)(img + IL.cls_cnt);
-    uint32_t* cls_list = (uint32_t*)(img + IL.cls_list);
 
     HostSlot& hs = host_slot();
     if (!hs.word) return LSR_EHIP;
     const uint32_t seq = ++hs.seq;
+    const HostWord hw{hs.dev, seq};
     if (bs.priv) {
         // per-block tile histograms -> column scan -> tile starts; M = total
         {
             StageScope sc(ST_DUP, st);
-            LSR_HIP(launch_bin_count(c, P, bs.chunk, bs.B, geom, out->radii, table, tile_cnt, tile_start, tpart,
-                                     cls_cnt, cls_list, hs.dev, seq, st));
+            LSR_HIP(launch_bin_count(c, P, geom, out->radii, ws, hw, st));
         }
         {
             StageScope sc(ST_SCAN_T, st);
-            LSR_HIP(launch_tile_start_apply(T, bs.B, tile_cnt, tpart, tile_start, st));
+            LSR_HIP(launch_tile_start_apply(T, ws, st));
         }
     } else {
         uint64_t* gpart = (uint64_t*)(geom + GL.scan_part);
@@ -367,7 +365,7 @@ int bin_tiles(const lsr_settings* s, const Cam& c, int P, const BinShape& bs, ui
         StageScope sc(ST_SCAN, st);
         LSR_HIP(launch_scan_u32((const uint32_t*)(geom + GL.tiles), (uint32_t*)(geom + GL.offsets), gpart,
                                 (size_t)P, false, st));
-        LSR_HIP(launch_publish_total(gpart + gnb, nullptr, hs.dev, seq, nullptr, st));
+        LSR_HIP(launch_publish_total(gpart + gnb, hw, st));
     }
     // speculative binning workspace sized from the previous call's M, taken
     // while the GPU is still counting, so the host usually has nothing but
@@ -398,21 +396,20 @@ int bin_tiles(const lsr_settings* s, const Cam& c, int P, const BinShape& bs, ui
     out->binning_bytes = bin_cap;
     if (bs.priv) {
         StageScope sc(ST_SCATTER, st);
-        LSR_HIP(launch_bin_scatter(c, P, bs.chunk, bs.B, geom, out->radii, table, tile_start,
-                                   (uint64_t*)(bin + BL.keys), st));
+        LSR_HIP(launch_bin_scatter(c, P, geom, out->radii, ws, (uint64_t*)(bin + BL.keys), st));
     } else {
         {
             StageScope sc(ST_DUP, st);
-            LSR_HIP(hipMemsetAsync(tile_cnt, 0, (size_t)T * 4, st));
-            LSR_HIP(launch_duplicate(c, P, geom, out->radii, tile_cnt, (uint32_t*)(bin + BL.rank), st));
+            LSR_HIP(hipMemsetAsync(ws.tile_cnt, 0, (size_t)T * 4, st));
+            LSR_HIP(launch_duplicate(c, P, geom, out->radii, ws.tile_cnt, (uint32_t*)(bin + BL.rank), st));
         }
         {
             StageScope sc(ST_SCAN_T, st);
-            LSR_HIP(launch_scan_u32(tile_cnt, tile_start, tpart, (size_t)T, true, st));
-            LSR_HIP(hipMemcpyAsync(tile_start + T, tpart + tnb, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            LSR_HIP(launch_scan_u32(ws.tile_cnt, ws.tile_start, ws.tpart, (size_t)T, true, st));
+            LSR_HIP(hipMemcpyAsync(ws.tile_start + T, ws.tpart + tnb, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         }
         StageScope sc(ST_SCATTER, st);
-        LSR_HIP(launch_scatter(c, P, geom, out->radii, tile_start, (const uint32_t*)(bin + BL.rank),
+        LSR_HIP(launch_scatter(c, P, geom, out->radii, ws.tile_start, (const uint32_t*)(bin + BL.rank),
                                (uint64_t*)(bin + BL.keys), st));
     }
     LSR_DEBUG_SYNC(s, st, "scatter");
@@ -432,8 +429,8 @@ int bin_tiles(const lsr_settings* s, const Cam& c, int P, const BinShape& bs, ui
     }
     {
         StageScope sc(ST_SORT, st);
-        LSR_HIP(launch_tile_sort(T, tile_start, (uint64_t*)(bin + BL.keys), (uint32_t*)(bin + BL.point_list), cls_cnt,
-                                 cls_list, bs.priv ? host_cls : nullptr, st));
+        LSR_HIP(launch_tile_sort(T, ws, (uint64_t*)(bin + BL.keys), (uint32_t*)(bin + BL.point_list),
+                                 bs.priv ? host_cls : nullptr, st));
     }
     LSR_DEBUG_SYNC(s, st, "tile_sort");
     return LSR_OK;

@@ -9,7 +9,7 @@ namespace lsr {
 Option g_options[kOptionEnd] = {
     {{0}, 0, -1},   // (no option 0)
     // LSR_OPT_BIN_MODE: the forward's tile binning; one mode is built (binning.hip:
-    // scatter into tile buckets + per-tile sort).  The depth-ordered mode of round 4
+    // scatter into tile buckets; tile_sort.hip: per-tile sort).  The depth-ordered mode of round 4
     // (order.hip) measured slower at every size (cfg5 scatter 4.55 vs 0.84 ms) and
     // was removed in round 5.
     {{LSR_BIN_AUTO}, LSR_BIN_AUTO, LSR_BIN_SORTED_TILES},

@@ -51,41 +51,63 @@ hipError_t launch_preprocess_bwd(const Cam& c, const lsr_inputs& in, const uint8
                                  const float* grad_acc, int VP, const lsr_bwd_out& out, hipStream_t st);
 hipError_t launch_mark_visible(int P, const float* means, const float* view, uint8_t* present, hipStream_t st);
 
-// binning.hip
+// scan.hip
 // Inclusive scan of n uint32 values (in-place allowed); writes the 64-bit total
 // to part[0] (part must hold scan_partials(n) uint64 entries).
 size_t scan_partials(size_t n);
 hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t* part, size_t n, bool exclusive, hipStream_t st);
-// Tile-sort size classes (binning.hip tile_class); their per-class tile counts
-// and lists live in the image workspace (cls_cnt, cls_list).
-#define SORT_NCLS 6
+
+// binning.hip
+// The binning's arrays in the image workspace and the privatised path's shape
+// (lsr_api.hip bin_tiles fills it once; T = gx gy tiles).
+struct BinWs {
+    int chunk, B;           // Gaussians per count chunk, chunks (bin_blocks; B >= 1 on the privatised path)
+    uint32_t* table;        // B x table_stride(T): per-chunk tile counts, then the chunks' bases
+    uint32_t* tile_cnt;     // T
+    uint32_t* tile_start;   // T + 1
+    uint64_t* tpart;        // the tile scan's partials / the 64-tile groups' bases
+    uint32_t* cls_cnt;      // SORT_NCLS class counts, LSR_TICKET_WORD, LSR_COUNT_WORD
+    uint32_t* cls_list;     // SORT_NCLS x T: the classes' tiles
+};
+// The coherent pinned host line M is published to (device view), with the
+// forward's sequence number (lsr_api.hip HostSlot).
+struct HostWord {
+    uint64_t* dev;
+    uint32_t seq;
+};
 #define LSR_TICKET_WORD 32   // cls_cnt word k_bin_table counts arrivals in (own 128-B line)
 #define LSR_COUNT_WORD 64    // cls_cnt words (one u64) k_bin_count sums M and arrivals in (own line;
                              // zeroed by the preprocess)
 #define LSR_CLS_SLOT 4       // pinned host word (u64 index) k_bin_table publishes the class counts under
-hipError_t launch_publish_total(const uint64_t* total, uint32_t* tile_end, uint64_t* host_slot, uint32_t seq,
-                                const uint32_t* cls_cnt, hipStream_t st);
+                             // (the counts themselves: u32 words 2 .. 1 + SORT_NCLS of the line)
+hipError_t launch_publish_total(const uint64_t* total, const HostWord& hw, hipStream_t st);
 hipError_t launch_duplicate(const Cam& c, int P, const uint8_t* geom, const int32_t* radii, uint32_t* tile_cnt,
                             uint32_t* rank, hipStream_t st);
 hipError_t launch_scatter(const Cam& c, int P, const uint8_t* geom, const int32_t* radii, const uint32_t* tile_start,
                           const uint32_t* rank, uint64_t* keys, hipStream_t st);
 int bin_blocks(int P, const Cam& c, int& chunk);
 bool bin_privatised_ok(const Cam& c);
-// count + column scan + group-level tile scan; publishes M (and the sort
-// class counts) to host_slot like launch_publish_total
-hipError_t launch_bin_count(const Cam& c, int P, int chunk, int B, const uint8_t* geom, const int32_t* radii,
-                            uint32_t* table, uint32_t* tile_cnt, uint32_t* tile_start, uint64_t* tpart,
-                            uint32_t* cls_cnt, uint32_t* cls_list, uint64_t* host_slot, uint32_t seq, hipStream_t st);
+// count + column scan + group-level tile scan; publishes M (word 0) and then
+// M with the sort class counts (word LSR_CLS_SLOT) to the host line
+hipError_t launch_bin_count(const Cam& c, int P, const uint8_t* geom, const int32_t* radii, const BinWs& ws,
+                            const HostWord& hw, hipStream_t st);
 int bin_scatter_rows(const Cam& c);
 int scatter_merge(int P);
 int bin_block(int P);
 // tile_start[0..T) from tile_cnt and the group bases launch_bin_count left in tpart
-hipError_t launch_tile_start_apply(int T, int B, const uint32_t* tile_cnt, const uint64_t* tpart, uint32_t* tile_start,
-                                   hipStream_t st);
-hipError_t launch_bin_scatter(const Cam& c, int P, int chunk, int B, const uint8_t* geom, const int32_t* radii,
-                              const uint32_t* table, const uint32_t* tile_start, uint64_t* keys, hipStream_t st);
-hipError_t launch_tile_sort(int T, const uint32_t* tile_start, uint64_t* keys, uint32_t* point_list,
-                            uint32_t* cls_cnt, uint32_t* cls_list, const uint32_t* host_cnt, hipStream_t st);
+hipError_t launch_tile_start_apply(int T, const BinWs& ws, hipStream_t st);
+hipError_t launch_bin_scatter(const Cam& c, int P, const uint8_t* geom, const int32_t* radii, const BinWs& ws,
+                              uint64_t* keys, hipStream_t st);
+
+// tile_sort.hip
+// Tile-sort size classes (tile_sort.h tile_class); their per-class tile counts
+// and lists live in the image workspace (BinWs::cls_cnt, cls_list).
+#define SORT_NCLS 5
+// host_cnt: the per-class tile counts when the host already has them (the
+// privatised binning path publishes them with M); null = unknown, the lists
+// are built here and every class runs a persistent grid.
+hipError_t launch_tile_sort(int T, const BinWs& ws, uint64_t* keys, uint32_t* point_list, const uint32_t* host_cnt,
+                            hipStream_t st);
 
 
 // render_fwd.hip, render_quick.hip (the forward render; RenderArgs is also the

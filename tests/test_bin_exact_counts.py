@@ -6,8 +6,9 @@ puts a chosen number of keys into every tile, so every keys-per-lane count,
 both sides of every 64-key boundary and the 1024 / 1025 class boundary are
 hit, with equal depths in every tile (the id breaks the tie), 28 count chunks
 that all have instances in the same tiles, a tile count (56) that is no
-multiple of 64 or 4, and empty tiles.  The other two are a two-band frame and a
-single-tile frame.  All against the oracle: radii, ranges, point_list,
+multiple of 64 or 4, and empty tiles.  A second frame of the same construction
+puts the upper sort classes at their exact boundaries (BIG_TARGETS).  The other
+two are a two-band frame and a single-tile frame.  All against the oracle: radii, ranges, point_list,
 n_contrib, images (the checks of test_gpu_parity's forward comparison).  Runs
 on the GPU box."""
 import numpy as np
@@ -23,17 +24,22 @@ W, H, GX, GY = 128, 112, 8, 7
 # keys per tile: 1, 2, both sides of every 64-key boundary up to 1024, a tile in
 # the middle of a keys-per-lane step and one of the first 4-wave class
 TARGETS = [1, 2] + [64 * r + d for r in range(1, 17) for d in (-1, 0, 1)] + [600, 1500]
+# both sides of every class boundary above 1024 (2048, 4096: the 4-wave block
+# sorts; 8192: the chunked sort), a chunked-sort tile of three 4096-key chunks
+# and one of five, whose last merge stage spans 32768 slots
+BIG_TARGETS = [2048, 2049, 4096, 4097, 8192, 8193, 12000, 16385]
 
 
-def exact_count_case(seed=0):
+def exact_count_case(seed=0, targets=TARGETS):
     """Tile t holds exactly n_t Gaussians, all projected to its centre pixel
     (7.5, 7.5) and far smaller than a tile; in each tile the first n/8 depths
-    repeat the next n/8 (the id breaks the tie); four tiles stay empty."""
+    repeat the next n/8 (the id breaks the tie); the tiles past the targets
+    stay empty (four with TARGETS)."""
     rng = np.random.default_rng(seed)
     cam = make_camera(W, H, yaw_deg=0.0)
     tiles = rng.permutation(GX * GY)
     counts = np.zeros(GX * GY, dtype=np.int64)
-    counts[tiles[:len(TARGETS)]] = TARGETS
+    counts[tiles[:len(targets)]] = targets
     xs, ys, zs = [], [], []
     for t in range(GX * GY):
         n = int(counts[t])
@@ -83,6 +89,25 @@ def test_exact_tile_counts(gpu, oracle_lib):
     got = run_gpu_forward(case, gpu)
     assert_forward(case, ref, got)
     # the in-bucket order before the sort is free to vary from launch to launch; the sorted lists must not
+    again = run_gpu_forward(case, gpu)
+    np.testing.assert_array_equal(again["point_list"], got["point_list"])
+    np.testing.assert_array_equal(again["ranges"], got["ranges"])
+
+
+def test_exact_tile_counts_upper_classes(gpu, oracle_lib):
+    """The classes above the one-wave sort at their exact boundaries: 2048 / 2049
+    and 4096 / 4097 (k_tile_sort_blk<8> | <16> | <32>), 8192 / 8193 (the last block
+    sort | k_tile_sort_big), and chunked sorts of three and of five chunks."""
+    case, counts = exact_count_case(seed=1, targets=BIG_TARGETS)
+    N = case["g"]["means3D"].shape[0]
+    assert N == 57060 == sum(BIG_TARGETS)
+    ref = oracle_lib.forward(oracle_problem(case))
+    assert ref["num_rendered"] == 57060
+    rr = np.asarray(ref["ranges"]).reshape(GX * GY, 2).astype(np.int64)
+    np.testing.assert_array_equal(rr[:, 1] - rr[:, 0], counts)
+    assert int((counts == 0).sum()) == 48
+    got = run_gpu_forward(case, gpu)
+    assert_forward(case, ref, got)
     again = run_gpu_forward(case, gpu)
     np.testing.assert_array_equal(again["point_list"], got["point_list"])
     np.testing.assert_array_equal(again["ranges"], got["ranges"])

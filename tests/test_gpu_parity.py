@@ -165,8 +165,8 @@ def test_big_tile_global_sort(gpu, oracle_lib):
 
 @pytest.mark.parametrize("N,W,H,lo,hi", [(4000, 48, 32, 512, 1024), (14000, 64, 48, 1024, 2048)])
 def test_tile_sort_size_classes(gpu, oracle_lib, N, W, H, lo, hi):
-    """Tiles of 513-1024 instances (one wave, 16 keys per lane) and of
-    1025-2048 (one wave, 32 keys per lane): bit-exact lists."""
+    """Tiles of 513-1024 instances (class 0: one wave, up to 16 keys per lane)
+    and of 1025-2048 (class 1: a 4-wave workgroup, 8 keys per lane): bit-exact lists."""
     case = make_case(N=N, W=W, H=H, sh_degree=None, seed=12)
     ref, got = _fwd_compare(case, gpu, oracle_lib)
     counts = ref["ranges"][:, 1] - ref["ranges"][:, 0]

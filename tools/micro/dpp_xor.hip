@@ -1,4 +1,4 @@
-// Checks the lane-exchange paths of the wave sort (binning.hip xor_lane_u32)
+// Checks the lane-exchange paths of the wave sort (tile_sort.hip xor_lane_u64; lsr_device.h xor_lane_u32)
 // against __shfl_xor on the GPU: every lane's partner value for M = 1..32.
 // Build: hipcc --offload-arch=gfx950 -O3 dpp_xor.hip -o dpp_xor ; run: ./dpp_xor
 #include <hip/hip_runtime.h>

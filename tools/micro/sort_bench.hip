@@ -4,7 +4,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../langsplatv2_amd/csrc
 //        sort_bench.hip -o sort_bench   (SORT_PERSISTENT=1: classify on the GPU, persistent grids)
 // Usage: ./sort_bench T lo hi [iters]   (tile sizes uniform in [lo, hi])
-#include "../../langsplatv2_amd/csrc/binning.hip"
+#include "../../langsplatv2_amd/csrc/tile_sort.hip"
 #include <algorithm>
 #include <cstring>
 #include <cstdio>
@@ -40,11 +40,10 @@ int main(int argc, char** argv)
     CK(hipMalloc(&d_out, M * 4));
     CK(hipMemcpy(d_start, start.data(), (T + 1) * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_keys0, keys.data(), M * 8, hipMemcpyHostToDevice));
-    // class lists as k_bin_table builds them (host copy of tile_class)
+    // class lists as k_bin_table builds them
     std::vector<uint32_t> cnt(SORT_NCLS, 0), list((size_t)SORT_NCLS * T, 0);
     for (int t = 0; t < T; t++) {
-        const int n = (int)(start[t + 1] - start[t]);
-        const int c = n <= 0 ? -1 : n <= 512 ? 0 : n <= 1024 ? 1 : n <= 2048 ? 2 : n <= 4096 ? 3 : n <= 8192 ? 4 : 5;
+        const int c = lsr::tile_class((int)(start[t + 1] - start[t]));
         if (c >= 0) list[(size_t)c * T + cnt[c]++] = t;
     }
     uint32_t *d_cnt, *d_list;
@@ -53,6 +52,10 @@ int main(int argc, char** argv)
     CK(hipMemcpy(d_cnt, cnt.data(), SORT_NCLS * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice));
     const bool persistent = getenv("SORT_PERSISTENT") != nullptr;
+    lsr::BinWs ws{};
+    ws.tile_start = d_start;
+    ws.cls_cnt = d_cnt;
+    ws.cls_list = d_list;
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
@@ -60,7 +63,7 @@ int main(int argc, char** argv)
     for (int it = 0; it < iters + 2; it++) {
         CK(hipMemcpy(d_keys, d_keys0, M * 8, hipMemcpyDeviceToDevice));
         CK(hipEventRecord(e0, 0));
-        CK(lsr::launch_tile_sort(T, d_start, d_keys, d_out, d_cnt, d_list, persistent ? nullptr : cnt.data(), 0));
+        CK(lsr::launch_tile_sort(T, ws, d_keys, d_out, persistent ? nullptr : cnt.data(), 0));
         CK(hipEventRecord(e1, 0));
         CK(hipEventSynchronize(e1));
         float ms;

@@ -6,7 +6,7 @@
 // keys span.  Every tile is checked against std::sort.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../langsplatv2_amd/csrc sort_radix.hip -o sort_radix
 // Usage: ./sort_radix T lo hi [iters]
-#include "../../langsplatv2_amd/csrc/binning.hip"
+#include "../../langsplatv2_amd/csrc/tile_sort.hip"
 #include <rocprim/block/block_radix_sort.hpp>
 #include <algorithm>
 #include <cstdio>
@@ -100,11 +100,10 @@ int main(int argc, char** argv)
     CK(hipMemcpy(d_keys0, keys.data(), M * 8, hipMemcpyHostToDevice));
     std::vector<uint32_t> cnt(SORT_NCLS, 0), list((size_t)SORT_NCLS * T, 0);
     for (int t = 0; t < T; t++) {
-        const int n = (int)(start[t + 1] - start[t]);
-        const int c = n <= 0 ? -1 : n <= 512 ? 0 : n <= 1024 ? 1 : n <= 2048 ? 2 : n <= 4096 ? 3 : n <= 8192 ? 4 : 5;
+        const int c = lsr::tile_class((int)(start[t + 1] - start[t]));
         if (c >= 0) list[(size_t)c * T + cnt[c]++] = t;
     }
-    if (cnt[2] != (uint32_t)T) { printf("sizes must all be in (1024, 2048]\n"); return 1; }
+    if (cnt[1] != (uint32_t)T) { printf("sizes must all be in (1024, 2048]\n"); return 1; }
     uint32_t *d_cnt, *d_list;
     CK(hipMalloc(&d_cnt, SORT_NCLS * 4));
     CK(hipMalloc(&d_list, list.size() * 4));
@@ -140,8 +139,12 @@ int main(int argc, char** argv)
         printf("%-34s best %.4f ms  %.1f GB/s(12B/key)  mismatches=%zu\n", name, best, M * 12.0 / best / 1e6, bad);
     };
     printf("T=%d sizes=[%d,%d] M=%zu\n", T, lo, hi, M);
-    run("shipped (bitonic + merge path)", [&] { CK(lsr::launch_tile_sort(T, d_start, d_keys, d_out, d_cnt, d_list, cnt.data(), 0)); });
-    const uint32_t* l2 = d_list + 2 * (size_t)T;
+    lsr::BinWs ws{};
+    ws.tile_start = d_start;
+    ws.cls_cnt = d_cnt;
+    ws.cls_list = d_list;
+    run("shipped (bitonic + merge path)", [&] { CK(lsr::launch_tile_sort(T, ws, d_keys, d_out, cnt.data(), 0)); });
+    const uint32_t* l2 = d_list + 1 * (size_t)T;   // the class-1 list: every tile
     const int g = std::min(T, 256 * 6);
     run("radix 64-bit, 8 bits/pass", [&] { k_radix<8, false><<<g, 256>>>(T, d_start, d_keys, d_out, l2, T); });
     run("radix 64-bit, 4 bits/pass", [&] { k_radix<4, false><<<g, 256>>>(T, d_start, d_keys, d_out, l2, T); });
