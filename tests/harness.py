@@ -91,6 +91,77 @@ def add_needles(case, frac=0.25, seed=0, sigma_px=(60.0, 600.0), angle_deg=(30.0
     return case
 
 
+def trained_regime(case, factor, seed=0):
+    """Turn a make_case frame into the regime of a trained scene: big, overlapping
+    splats (every scale x `factor`), pixels that terminate early, saturated
+    alphas, clamped SH colours and the projection's clamp quirk.  Works in camera
+    space and rotates positions into the world by the view rotation, as
+    make_gaussians does.  Rows 0..20 are overwritten:
+      0..11   beyond the 1.3 tanfov clamp of t.x / t.z (even rows) and t.y / t.z
+              (odd rows): |x/z| = 1.45 tanfov, z = 3 + k/2, scales 0.6..0.7,
+              opacity 0.8 (test_oracle._grow's construction, on both axes);
+      12      one giant, scales (5, 4, 3) (axis-aligned) at z = 4, opacity 0.3:
+              it touches every tile of the frame;
+      13..16  on the optical axis at view-space z = nextafter(0.2f, 1), 0.2f,
+              nextafter(0.2f, 0), 0.25: around the near-plane cull (the positions
+              are rotated into the world in float64 and rounded to fp32, so the
+              kernel's fp32 view-space z is exactly these values only where the
+              view rotation is the identity; in a yawed frame the rows lie within
+              an ulp or two of the plane, on whichever side the rounding puts them);
+      17..20  medium splats near the centre with opacity 0, 1/255,
+              nextafter(1/255f, 1), 1: the alpha threshold and the 0.99 clamp.
+    Of the other rows a seeded 15 % get opacity 0.999, and (SH input) a seeded
+    25 % get 1.8 subtracted from their DC coefficients, so whole colours clamp
+    at 0.  With cov3D_precomp the special rows' covariances are the diagonal
+    ones of the same scale triples."""
+    g, cam = case["g"], case["cam"]
+    N = g["means3D"].shape[0]
+    S = 21
+    assert N > 2 * S
+    rng = np.random.default_rng(seed)
+    tx, ty = cam["tanfovx"], cam["tanfovy"]
+    if "scales" in g:
+        g["scales"] = g["scales"] * factor
+    else:
+        g["cov3D_precomp"] = g["cov3D_precomp"] * (factor * factor)
+    pos = np.zeros((S, 3), np.float64)
+    sc = np.zeros((S, 3), np.float32)
+    op = np.zeros(S, np.float32)
+    for k in range(12):
+        z = 3.0 + 0.5 * k
+        sgn = 1.0 if (k // 2) % 2 == 0 else -1.0
+        off = 0.3 * (k % 3 - 1)
+        pos[k] = (sgn * 1.45 * z * tx, off * z * ty, z) if k % 2 == 0 else (off * z * tx, sgn * 1.45 * z * ty, z)
+        sc[k] = 0.6 + 0.1 * rng.random(3)
+        op[k] = 0.8
+    pos[12], sc[12], op[12] = (0.0, 0.0, 4.0), (5.0, 4.0, 3.0), 0.3
+    near = np.float32(0.2)
+    for j, z in enumerate((np.nextafter(near, np.float32(1)), near, np.nextafter(near, np.float32(0)),
+                           np.float32(0.25))):
+        pos[13 + j], sc[13 + j], op[13 + j] = (0.0, 0.0, float(z)), 0.002, 0.6
+    thr = np.float32(1.0 / 255.0)
+    for j, o in enumerate((np.float32(0.0), thr, np.nextafter(thr, np.float32(1)), np.float32(1.0))):
+        pos[17 + j], sc[17 + j], op[17 + j] = ((j - 1.5) * 0.25, (1.5 - j) * 0.1, 5.0), (0.2, 0.15, 0.1), o
+    wv = cam["viewmatrix"].cpu().t()[:3, :3].double()
+    g["means3D"][:S] = (torch.from_numpy(pos) @ wv).float()
+    g["opacities"][:S, 0] = torch.from_numpy(op)
+    if "scales" in g:
+        g["scales"][:S] = torch.from_numpy(sc)
+        g["rotations"][12] = torch.tensor([1.0, 0.0, 0.0, 0.0])
+    else:
+        s2 = (torch.from_numpy(sc).double() * case["scale_modifier"]) ** 2
+        cov = torch.zeros(S, 6, dtype=torch.float64)
+        cov[:, 0], cov[:, 3], cov[:, 5] = s2[:, 0], s2[:, 1], s2[:, 2]
+        g["cov3D_precomp"][:S] = cov.float()
+    rest = np.arange(S, N)
+    opaque = np.sort(rng.choice(rest, size=int(round(0.15 * rest.size)), replace=False))
+    g["opacities"][opaque] = 0.999
+    if "shs" in g:
+        dark = np.sort(rng.choice(rest, size=int(round(0.25 * rest.size)), replace=False))
+        g["shs"][dark, 0] -= 1.8
+    return case
+
+
 def cov3d_torch(s, q):
     q = q.double()
     r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
@@ -127,23 +198,29 @@ def gpu_inputs(case, device, requires_grad=True):
     return t
 
 
-def run_gpu_forward(case, device, lang_layout=None):
+def run_gpu_forward(case, device, lang_layout=None, grad_request=0):
     """Forward through the library with workspace buffers decoded (lang_layout:
     the quick map's language_feature_layout: "chw" the reference's (Dq,H,W), None the
-    default (pixel-major where the 12-code kernel applies), "hwc" pixel-major)."""
-    from langsplatv2_amd import layout, rasterizer
+    default (pixel-major where the 12-code kernel applies), "hwc" pixel-major).
+    grad_request (LSR_GWS_* bits): the forward of a call with a pending backward,
+    as autograd runs it in training -- the render instantiation that also zeroes
+    the backward's accumulators and, within the LSR_OPT_LISTS_MAX_MB budget,
+    writes the per-block candidate lists; 0 is the inference forward.  The result
+    says what that forward handed over: "has_grad_ws", "has_lists"."""
+    from langsplatv2_amd import _lib, layout, rasterizer
     rs = settings_for(case, device, lang_layout)
     t = gpu_inputs(case, device, requires_grad=False)
     e = torch.empty(0, device=device)
-    color, lang, radii, M, bufs, _, _, _ = rasterizer._run_forward(
+    color, lang, radii, M, bufs, _, _, ws = rasterizer._run_forward(
         t["means3D"], t.get("shs", e), t.get("colors_precomp", e), t.get("language_feature_precomp", e),
         t.get("language_feature_weights_quick", e), t.get("language_feature_indices", e), t["opacities"],
-        t.get("scales", e), t.get("rotations", e), t.get("cov3D_precomp", e), rs)
+        t.get("scales", e), t.get("rotations", e), t.get("cov3D_precomp", e), rs, grad_request)
     torch.cuda.synchronize()
     N = t["means3D"].shape[0]
     dec = layout.decode(bufs, N, rs.image_width, rs.image_height, M)
     out = {k: v.cpu().numpy() for k, v in dec.items()}
-    out.update(color=color.cpu().numpy(), lang=lang.cpu().numpy(), radii=radii.cpu().numpy(), num_rendered=M)
+    out.update(color=color.cpu().numpy(), lang=lang.cpu().numpy(), radii=radii.cpu().numpy(), num_rendered=M,
+               has_grad_ws=ws is not None, has_lists=bufs.get(_lib.LSR_BUF_LISTS) is not None)
     return out
 
 
@@ -249,7 +326,8 @@ def run_gpu_bwd_rows(case, device, dout_color, dout_lang=None, deterministic=Tru
     workspace the backward accumulates into (the deterministic backward's
     conversion pass writes every element of it) -- [0,1] dL/dmeans2D (NDC),
     [2..4] dL/dconic, [5] dL/dopacity, [6..8] dL/dcolour, lang columns per
-    layout.  Returns {"rows": (N, VP), "VP": VP, "grad_<input>": ...}."""
+    layout.  Returns {"rows": (N, VP), "VP": VP, "grad_<input>": ..., "has_lists":
+    whether the forward handed the backward its per-block candidate lists}."""
     from types import SimpleNamespace
 
     from langsplatv2_amd import _lib, rasterizer
@@ -279,7 +357,7 @@ def run_gpu_bwd_rows(case, device, dout_color, dout_lang=None, deterministic=Tru
     N = t["means3D"].shape[0]
     VP = ws[1] // (4 * N)
     out = dict(rows=ws[0][:N * VP * 4].view(torch.float32).view(N, VP).cpu().numpy(), VP=VP,
-               radii=radii.cpu().numpy(), num_rendered=M)
+               radii=radii.cpu().numpy(), num_rendered=M, has_lists=ctx.saved_tensors[-1] is not None)
     names = ("means3D", "means2D", "shs", "colors_precomp", "language_feature_precomp", None, None, "opacities",
              "scales", "rotations", "cov3D_precomp")
     for nm, v in zip(names, g):

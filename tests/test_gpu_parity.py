@@ -30,10 +30,11 @@ CASES = {
 }
 
 
-def _fwd_compare(case, gpu, oracle_lib):
+def _fwd_compare(case, gpu, oracle_lib, grad_request=0):
+    """grad_request: see harness.run_gpu_forward (0: the inference forward)."""
     pb = oracle_problem(case)
     ref = oracle_lib.forward(pb)
-    got = run_gpu_forward(case, gpu)
+    got = run_gpu_forward(case, gpu, grad_request=grad_request)
     vis = ref["radii"] > 0
     np.testing.assert_array_equal(got["radii"], ref["radii"])
     np.testing.assert_array_equal(got["tiles_touched"], ref["tiles_touched"].astype(np.int32))
