@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_photo_loss_forward / _backward;
+#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_kmeans_workspace_bytes / _prepare / _assign / _update;
+                               12, additive (no bump): lsr_photo_loss_forward / _backward;
                                12, additive (no bump): lsr_quick_heat_plan_bytes / _prepare / _run, lsr_heat_frame;
                                12, additive (no bump): lsr_query_post_workspace_bytes, lsr_query_smooth, lsr_query_mask;
                                12, additive (no bump): lsr_quick_query_plan_bytes / _prepare / _run;
@@ -446,6 +447,37 @@ int lsr_photo_loss_forward(const float* image, const float* gt, int planes, int 
 int lsr_photo_loss_backward(const float* image, const float* gt, int planes, int H, int W,
                             const float* partials, const float* grad_out /* device float[2] */,
                             float* grad_image, void* stream);
+
+/* k-means codebook initialisation of the feature phase: Lloyd's iteration over
+ * the (M, D) fp32 table of 2-D language features, per level what
+ * ResidualVectorQuantizationWithClustering.fit_quantizers (utils/vq_utils.py:43-104,
+ * train.py:78-85) does on the host with sklearn and an M x K torch.cdist.
+ *
+ * lsr_kmeans_prepare lays the (K, D) centres out for the search in workspace
+ * (lsr_kmeans_workspace_bytes(M, K, D) bytes, device, 256-B aligned; the part it
+ * writes does not depend on M).  lsr_kmeans_assign then gives per row the
+ * nearest prepared centre by score_k = |c_k|^2 - 2 x.c_k (exact-f32 MFMA, ties
+ * to the lowest index, as numpy / torch argmin on CPU): assign (M) int32, dist
+ * (M) = max(score + |x|^2, 0), and optionally residual_out (M, D) = x -
+ * c[assign] (must not alias x).  lsr_kmeans_update forms centers_out (K, D) =
+ * the mean of each cluster's rows and counts_out (K) int32 from x and assign
+ * (an index outside [0, K) is skipped); a cluster without rows keeps its
+ * prepared centre and reports 0.  It then prepares centers_out in workspace,
+ * so assign / update alternate with no further call.  No float atomics and a
+ * split that depends on (M, K, D) only: bit-identical from run to run.
+ *
+ * LSR_EINVAL: K outside 1..256, D outside 4..1024 or not a multiple of 4, M < 0
+ * or M >= 2^31, a NULL or not 16-B aligned x, centers, workspace or
+ * centers_out, a residual_out that is not 16-B aligned or equals x, a NULL
+ * assign, dist or counts_out.  M = 0 is a no-op
+ * (nothing is read or written).  lsr_kmeans_workspace_bytes returns 0 for a
+ * shape that is not taken.  Additive to ABI 12. */
+size_t lsr_kmeans_workspace_bytes(int64_t M, int K, int D);
+int lsr_kmeans_prepare(const float* centers, int K, int D, void* workspace, void* stream);
+int lsr_kmeans_assign(const float* x, int64_t M, int D, int K, const void* workspace, int32_t* assign, float* dist,
+                      float* residual_out /* (M, D) or NULL */, void* stream);
+int lsr_kmeans_update(const float* x, const int32_t* assign, int64_t M, int D, int K, void* workspace,
+                      float* centers_out, int32_t* counts_out, void* stream);
 
 /* Fused Adam step: the update of torch.optim.Adam as the
  * reference builds it (scene/gaussian_model.py:234-255, no amsgrad), one pass

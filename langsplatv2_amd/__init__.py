@@ -7,6 +7,8 @@ gaussian_renderer/__init__.py and train.py run unchanged.  Compute is in
 liblsr.so (C ABI: include/lsr.h).
 """
 from ._lib import deterministic, set_deterministic  # noqa: F401
+from .codebook_init import (ResidualVectorQuantizationWithClustering, assign_codes, fit_codebooks,  # noqa: F401
+                            kmeans_step, quantize)
 from .densify import (DensifyResult, densify_and_prune, densify_and_prune_torch, densify_tensors,  # noqa: F401
                       reset_opacity)
 from .heatmap import (QuickHeatStream, heat_frames, heat_plan, jet_lut, mean_relevancy_maps,  # noqa: F401
@@ -23,4 +25,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "smooth_maps", "segment_maps", "localize_maps", "hits", "SegmentResult", "LocalizeResult",
            "summed_similarity_maps", "mean_relevancy_maps", "heat_frames", "jet_lut", "heat_plan", "QuickHeatStream",
            "photometric_loss", "l1_ssim", "densify_tensors", "densify_and_prune", "densify_and_prune_torch", "reset_opacity",
-           "DensifyResult"]
+           "DensifyResult", "assign_codes", "kmeans_step", "quantize", "fit_codebooks",
+           "ResidualVectorQuantizationWithClustering"]

@@ -48,6 +48,12 @@ PhotoTaps photo_taps()
     return t;
 }
 
+// every shape the k-means kernels do not take is an invalid argument
+int kmeans_args(int64_t M, int K, int D)
+{
+    return M < 0 || M > 0x7fffffffLL || K < 1 || K > 256 || D < 4 || D > 1024 || (D % 4) != 0 ? LSR_EINVAL : LSR_OK;
+}
+
 // a code count the kernels are not built for is unsupported, anything else invalid
 int topk_code_args(int64_t N, int L, int K, int k)
 {
@@ -293,6 +299,41 @@ int lsr_photo_loss_backward(const float* image, const float* gt, int planes, int
     LSR_TRY(photo_loss_args(image, gt, planes, H, W));
     LSR_HIP(launch_photo_loss_bwd(image, gt, planes, H, W, photo_taps(), partials, grad_out, grad_image,
                                   (hipStream_t)stream));
+    return LSR_OK;
+}
+
+size_t lsr_kmeans_workspace_bytes(int64_t M, int K, int D)
+{
+    return kmeans_args(M, K, D) != LSR_OK ? 0 : kmeans_workspace_bytes(M, K, D);
+}
+
+int lsr_kmeans_prepare(const float* centers, int K, int D, void* workspace, void* stream)
+{
+    LSR_TRY(kmeans_args(0, K, D));
+    if (!centers || !workspace || misaligned16(centers) || misaligned16(workspace)) return LSR_EINVAL;
+    LSR_HIP(launch_kmeans_prepare(centers, K, D, workspace, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_kmeans_assign(const float* x, int64_t M, int D, int K, const void* workspace, int32_t* assign, float* dist,
+                      float* residual_out, void* stream)
+{
+    LSR_TRY(kmeans_args(M, K, D));
+    if (M == 0) return LSR_OK;
+    if (!x || !workspace || !assign || !dist || residual_out == x) return LSR_EINVAL;
+    if (misaligned16(x) || misaligned16(workspace) || misaligned16(residual_out)) return LSR_EINVAL;
+    LSR_HIP(launch_kmeans_assign(x, (int)M, D, K, workspace, assign, dist, residual_out, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_kmeans_update(const float* x, const int32_t* assign, int64_t M, int D, int K, void* workspace,
+                      float* centers_out, int32_t* counts_out, void* stream)
+{
+    LSR_TRY(kmeans_args(M, K, D));
+    if (M == 0) return LSR_OK;
+    if (!x || !assign || !workspace || !centers_out || !counts_out) return LSR_EINVAL;
+    if (misaligned16(workspace) || misaligned16(centers_out)) return LSR_EINVAL;
+    LSR_HIP(launch_kmeans_update(x, assign, (int)M, D, K, workspace, centers_out, counts_out, (hipStream_t)stream));
     return LSR_OK;
 }
 

@@ -296,6 +296,19 @@ hipError_t launch_photo_loss_fwd(const float* x, const float* y, int planes, int
 hipError_t launch_photo_loss_bwd(const float* x, const float* y, int planes, int H, int W, const PhotoTaps& tp,
                                  const float* partials, const float* g, float* gx, hipStream_t st);
 
+// kmeans.hip: Lloyd's iteration over an (M, D) feature table (D % 4 == 0, 4 <= D <= 1024, 1 <= K <= 256, M < 2^31)
+size_t kmeans_workspace_bytes(int64_t M, int K, int D);
+// the centres' MFMA fragments, norms and raw copy into ws (once per centre set)
+hipError_t launch_kmeans_prepare(const float* centers, int K, int D, void* ws, hipStream_t st);
+// assign (M) = nearest prepared centre, ties to the lowest index; dist (M) = max(|x - c|^2, 0);
+// residual (M, D) = x - c[assign] or nullptr (must not alias x)
+hipError_t launch_kmeans_assign(const float* x, int M, int D, int K, const void* ws, int* assign, float* dist,
+                                float* residual, hipStream_t st);
+// centers_out (K, D) = per-cluster means (an empty cluster: its prepared centre), counts_out (K);
+// then prepares centers_out in ws
+hipError_t launch_kmeans_update(const float* x, const int* assign, int M, int D, int K, void* ws, float* centers_out,
+                                int* counts_out, hipStream_t st);
+
 // densify.hip: densify_and_prune as one gather (plan: classify, scan, fill; apply: all 18 tensors)
 struct DensifyArgs {
     float max_grad, dense_thresh, min_opacity, big_thresh;   // thresholds as the reference's fp32 comparisons see them

@@ -303,6 +303,40 @@ TABLE = [
     ("lsr_adam_step", (None, None, None, None, 0, 0.1, 0.9, 0.999, 1e-8, 0.0, 1, None), OK),
     ("lsr_adam_step", (P, P, P, None, 10, 0.1, 0.9, 0.999, 1e-8, 0.0, 1, None), EINVAL),
     ("lsr_mark_visible", (10, None, P, P, P, None), EINVAL),
+    # lsr_kmeans_prepare(centers, K, D, workspace, stream): every shape not taken is an invalid argument
+    ("lsr_kmeans_prepare", (None, 64, 512, P, None), EINVAL),
+    ("lsr_kmeans_prepare", (P, 64, 512, None, None), EINVAL),
+    ("lsr_kmeans_prepare", (P, 0, 512, P, None), EINVAL),
+    ("lsr_kmeans_prepare", (P, 257, 512, P, None), EINVAL),
+    ("lsr_kmeans_prepare", (P, 64, 6, P, None), EINVAL),
+    ("lsr_kmeans_prepare", (P, 64, 1028, P, None), EINVAL),
+    # lsr_kmeans_assign(x, M, D, K, workspace, assign, dist, residual_out, stream)
+    ("lsr_kmeans_assign", (None, 10, 512, 64, P, P, P, None, None), EINVAL),
+    ("lsr_kmeans_assign", (P, 10, 512, 64, None, P, P, None, None), EINVAL),
+    ("lsr_kmeans_assign", (P, 10, 512, 64, P, None, P, None, None), EINVAL),
+    ("lsr_kmeans_assign", (P, 10, 512, 64, P, P, None, None, None), EINVAL),
+    ("lsr_kmeans_assign", (P, 10, 512, 64, P, P, P, P, None), EINVAL),     # the residual may not alias x
+    ("lsr_kmeans_assign", (P, 10, 512, 0, P, P, P, None, None), EINVAL),
+    ("lsr_kmeans_assign", (P, 10, 512, 257, P, P, P, None, None), EINVAL),
+    ("lsr_kmeans_assign", (P, 10, 6, 64, P, P, P, None, None), EINVAL),
+    ("lsr_kmeans_assign", (P, 10, 1028, 64, P, P, P, None, None), EINVAL),
+    ("lsr_kmeans_assign", (P, -1, 512, 64, P, P, P, None, None), EINVAL),
+    ("lsr_kmeans_assign", (P, 1 << 31, 512, 64, P, P, P, None, None), EINVAL),
+    ("lsr_kmeans_assign", (None, 0, 512, 257, None, None, None, None, None), EINVAL),   # the shape before the no-op
+    ("lsr_kmeans_assign", (None, 0, 512, 64, None, None, None, None, None), OK),
+    # lsr_kmeans_update(x, assign, M, D, K, workspace, centers_out, counts_out, stream)
+    ("lsr_kmeans_update", (None, P, 10, 512, 64, P, P, P, None), EINVAL),
+    ("lsr_kmeans_update", (P, None, 10, 512, 64, P, P, P, None), EINVAL),
+    ("lsr_kmeans_update", (P, P, 10, 512, 64, None, P, P, None), EINVAL),
+    ("lsr_kmeans_update", (P, P, 10, 512, 64, P, None, P, None), EINVAL),
+    ("lsr_kmeans_update", (P, P, 10, 512, 64, P, P, None, None), EINVAL),
+    ("lsr_kmeans_update", (P, P, 10, 512, 0, P, P, P, None), EINVAL),
+    ("lsr_kmeans_update", (P, P, 10, 512, 257, P, P, P, None), EINVAL),
+    ("lsr_kmeans_update", (P, P, 10, 6, 64, P, P, P, None), EINVAL),
+    ("lsr_kmeans_update", (P, P, 10, 1028, 64, P, P, P, None), EINVAL),
+    ("lsr_kmeans_update", (P, P, -1, 512, 64, P, P, P, None), EINVAL),
+    ("lsr_kmeans_update", (None, None, 0, 6, 64, None, None, None, None), EINVAL),      # the shape before the no-op
+    ("lsr_kmeans_update", (None, None, 0, 512, 64, None, None, None, None), OK),
 ]
 for fn, args, want in TABLE:
     rc = getattr(lib, fn)(*args)
@@ -321,6 +355,10 @@ for args, some in [((3, 64, 512, 1, 0), True), ((1, 64, 16, 60, 4), True), ((4, 
     calls += 1
 for args, some in [((3, 64, 512, 0), True), ((-1, 64, 512, 1), False), ((3, 64, 24, 1), False), ((3, 128, 512, 1), False)]:
     assert (lib.lsr_quick_decode_plan_bytes(*args) > 0) == some, args
+    calls += 1
+for args, some in [((1000, 64, 512), True), ((0, 1, 4), True), ((10, 0, 512), False), ((10, 257, 512), False),
+                   ((10, 64, 6), False), ((10, 64, 1028), False), ((-1, 64, 512), False), ((1 << 31, 64, 512), False)]:
+    assert (lib.lsr_kmeans_workspace_bytes(*args) > 0) == some, args
     calls += 1
 for args, some in [((2, 4, 4), True), ((0, 4, 4), False), ((2, 0, 4), False), ((-1, 4, 4), False), ((70000, 4, 4), False)]:
     assert (lib.lsr_query_post_workspace_bytes(*args) > 0) == some, args
