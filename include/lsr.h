@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_kmeans_workspace_bytes / _prepare / _assign / _update;
+#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_mask_nms_workspace_bytes, lsr_mask_pack / _pair_counts / _nms_select / _segmaps;
+                               12, additive (no bump): lsr_kmeans_workspace_bytes / _prepare / _assign / _update;
                                12, additive (no bump): lsr_photo_loss_forward / _backward;
                                12, additive (no bump): lsr_quick_heat_plan_bytes / _prepare / _run, lsr_heat_frame;
                                12, additive (no bump): lsr_query_post_workspace_bytes, lsr_query_smooth, lsr_query_mask;
@@ -478,6 +479,65 @@ int lsr_kmeans_assign(const float* x, int64_t M, int D, int K, const void* works
                       float* residual_out /* (M, D) or NULL */, void* stream);
 int lsr_kmeans_update(const float* x, const int32_t* assign, int64_t M, int D, int K, void* workspace,
                       float* centers_out, int32_t* counts_out, void* stream);
+
+/* SAM mask NMS and segment maps of the preprocess step that writes
+ * <image>_s.npy: mask_nms (preprocess.py:215-279) and mask2segmap with create's
+ * level offsets (preprocess.py:304-317, :145-157), on bit-packed masks.
+ *
+ * lsr_mask_pack packs (N, H, W) bytes (nonzero = set) into words (N, W64),
+ * W64 = ceil(H W / 64): bit b of word w is pixel 64 w + b in row-major order,
+ * bits past H W are zero; area (N) is each mask's popcount.
+ * lsr_mask_pair_counts fills inter (N, N): inter[i][j] = |mask order[i] AND
+ * mask order[j]| for i <= j (order NULL: the identity), 0 below the diagonal.
+ * Integer accumulation only: exact and identical from run to run.
+ * lsr_mask_nms_select does the pair counts into workspace
+ * (lsr_mask_nms_workspace_bytes(N) bytes, device, 16-B aligned; it starts with
+ * the (N, N) int32 table) and then, in one launch with no host read-back,
+ * decides: order (N) is the rank order (scores descending, stable), conf (N)
+ * is per rank score > score_thr.  With I = inter[i][j], A = area, all fp32:
+ *   iou = f(I) / f(A_i + A_j - I),  a = f(I) / f(A_i),  b = f(I) / f(A_j),
+ *   U[i][j] = 1 - b a if a < 0.5 and b >= 0.85,  L[j][i] = 1 - b a if a >= 0.85 and b < 0.5,
+ *   iou_max[c] = max(0, max_{i<c} iou[i][c]),  u_max[c] = max(0, max_{i<c} U[i][c]),
+ *   l_max[c] = max(0, max_{r>c} L[r][c], U[c-1][c])   (the reference's tril(diagonal=1)),
+ *   keep[c] = iou_max[c] <= (float)iou_thr and conf[c] and u_max[c] <= cut and l_max[c] <= cut,
+ *   cut = (float)(1.0 - inner_thr);
+ * the maxima propagate NaN (an empty pair's 0 / 0 drops its column); a
+ * criterion among conf, inner-u, inner-l that no rank passes is set for ranks
+ * 0 .. min(3, N) - 1 instead.  keep (N) is per rank, criteria (N, or NULL) the
+ * LSR_MASK_CRIT_* bits per rank after the fallbacks, selected (N int64, the
+ * first *count valid) the kept input indices in rank order.  An order entry
+ * outside [0, N) reads as an empty mask.
+ * lsr_mask_segmaps writes out (4, H, W), fp32 (LSR_INDEX_F32) or int32
+ * (LSR_INDEX_I32): per level l the highest k < counts[l] whose mask kept[l][k]
+ * (of the masks[l] packed masks words[l]) covers the pixel, plus offsets[l];
+ * -1 where none does.  The four arrays are host arrays of 4; a level with
+ * counts[l] = 0 may have NULL pointers.
+ *
+ * LSR_EUNSUPPORTED: N (masks[l], counts[l]) > LSR_MASK_MAX_N, H W >
+ * LSR_MASK_MAX_PIXELS (every count must be exact in fp32).  LSR_EINVAL: N < 0,
+ * H or W < 1, a NULL or misaligned (words: 8 B, workspace: 16 B) pointer, a
+ * negative count or offset, an index_type other than the two.  N = 0 (pack,
+ * pair counts, select): LSR_OK, nothing is read or written.  All checks come
+ * before any device call.  lsr_mask_nms_workspace_bytes returns 0 for an N that
+ * is not taken.  Additive to ABI 12. */
+#define LSR_MASK_MAX_N 4096
+#define LSR_MASK_MAX_PIXELS (1 << 24)
+#define LSR_MASK_PAIR_TILE 64   /* masks per side of a pair-count tile */
+#define LSR_MASK_WORD_CHUNK 32  /* 64-bit words of each mask a pair-count step stages */
+#define LSR_MASK_CRIT_IOU 1
+#define LSR_MASK_CRIT_CONF 2
+#define LSR_MASK_CRIT_INNER_U 4
+#define LSR_MASK_CRIT_INNER_L 8
+size_t lsr_mask_nms_workspace_bytes(int N);
+int lsr_mask_pack(const uint8_t* masks, int N, int H, int W, uint64_t* words, int32_t* area, void* stream);
+int lsr_mask_pair_counts(const uint64_t* words, int N, int H, int W, const int32_t* order /* or NULL */,
+                         int32_t* inter, void* stream);
+int lsr_mask_nms_select(const uint64_t* words, const int32_t* area, int N, int H, int W, const int32_t* order,
+                        const uint8_t* conf, double iou_thr, double inner_thr, void* workspace, uint8_t* keep,
+                        uint8_t* criteria /* or NULL */, int64_t* selected, int32_t* count, void* stream);
+int lsr_mask_segmaps(const uint64_t* const* words, const int32_t* const* kept, const int32_t* masks,
+                     const int32_t* counts, const int32_t* offsets, int H, int W, int index_type, void* out,
+                     void* stream);
 
 /* Fused Adam step: the update of torch.optim.Adam as the
  * reference builds it (scene/gaussian_model.py:234-255, no amsgrad), one pass

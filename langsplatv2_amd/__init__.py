@@ -13,6 +13,8 @@ from .densify import (DensifyResult, densify_and_prune, densify_and_prune_torch,
                       reset_opacity)
 from .heatmap import (QuickHeatStream, heat_frames, heat_plan, jet_lut, mean_relevancy_maps,  # noqa: F401
                       summed_similarity_maps)
+from .mask_nms import (NmsResult, PackedMasks, build_seg_maps, mask_nms, mask_pair_counts,  # noqa: F401
+                       masks_update, pack_masks)
 from .photo_loss import l1_ssim, photometric_loss  # noqa: F401
 from .query import QuickRelevancyStream, query_plan, relevancy_maps, similarity_maps  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: F401
@@ -26,4 +28,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "summed_similarity_maps", "mean_relevancy_maps", "heat_frames", "jet_lut", "heat_plan", "QuickHeatStream",
            "photometric_loss", "l1_ssim", "densify_tensors", "densify_and_prune", "densify_and_prune_torch", "reset_opacity",
            "DensifyResult", "assign_codes", "kmeans_step", "quantize", "fit_codebooks",
-           "ResidualVectorQuantizationWithClustering"]
+           "ResidualVectorQuantizationWithClustering", "pack_masks", "mask_pair_counts", "mask_nms", "masks_update",
+           "build_seg_maps", "PackedMasks", "NmsResult"]

@@ -135,6 +135,8 @@ EXPORTS = ("lsr_forward", "lsr_backward", "lsr_mark_visible", "lsr_quick_decode"
            "lsr_quick_pack_codes", "lsr_topk_code_forward",
            "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_photo_loss_forward", "lsr_photo_loss_backward",
            "lsr_kmeans_workspace_bytes", "lsr_kmeans_prepare", "lsr_kmeans_assign", "lsr_kmeans_update",
+           "lsr_mask_nms_workspace_bytes", "lsr_mask_pack", "lsr_mask_pair_counts", "lsr_mask_nms_select",
+           "lsr_mask_segmaps",
            "lsr_densify_workspace_bytes", "lsr_densify_plan", "lsr_densify_apply", "lsr_reset_opacity", "lsr_adam_step", "lsr_sh_grad_from_views", "lsr_strerror",
            "lsr_abi_version", "lsr_max_lang_dim", "lsr_profile_enable", "lsr_profile_stages", "lsr_profile_reset",
            "lsr_profile_query", "lsr_set_option", "lsr_get_option", "lsr_stream_create", "lsr_stream_destroy")
@@ -232,6 +234,17 @@ def load(path: str | None = None):
     lib.lsr_kmeans_assign.restype = ctypes.c_int
     lib.lsr_kmeans_update.argtypes = [_vp, _vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp]
     lib.lsr_kmeans_update.restype = ctypes.c_int
+    _cd = ctypes.c_double
+    lib.lsr_mask_nms_workspace_bytes.argtypes = [_ci]
+    lib.lsr_mask_nms_workspace_bytes.restype = ctypes.c_size_t
+    lib.lsr_mask_pack.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp]
+    lib.lsr_mask_pack.restype = ctypes.c_int
+    lib.lsr_mask_pair_counts.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp]
+    lib.lsr_mask_pair_counts.restype = ctypes.c_int
+    lib.lsr_mask_nms_select.argtypes = [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.lsr_mask_nms_select.restype = ctypes.c_int
+    lib.lsr_mask_segmaps.argtypes = [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp]
+    lib.lsr_mask_segmaps.restype = ctypes.c_int
     lib.lsr_densify_workspace_bytes.argtypes = [_i64]
     lib.lsr_densify_workspace_bytes.restype = ctypes.c_size_t
     lib.lsr_densify_plan.argtypes = [_i64, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _ci, _cf, _vp,

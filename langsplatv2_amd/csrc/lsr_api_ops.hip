@@ -54,6 +54,15 @@ int kmeans_args(int64_t M, int K, int D)
     return M < 0 || M > 0x7fffffffLL || K < 1 || K > 256 || D < 4 || D > 1024 || (D % 4) != 0 ? LSR_EINVAL : LSR_OK;
 }
 
+// a mask count or frame beyond what the mask kernels are built for is unsupported, anything else invalid
+int mask_args(int N, int H, int W)
+{
+    if (N < 0 || H < 1 || W < 1) return LSR_EINVAL;
+    return N > LSR_MASK_MAX_N || (int64_t)H * W > LSR_MASK_MAX_PIXELS ? LSR_EUNSUPPORTED : LSR_OK;
+}
+
+bool misaligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
+
 // a code count the kernels are not built for is unsupported, anything else invalid
 int topk_code_args(int64_t N, int L, int K, int k)
 {
@@ -334,6 +343,64 @@ int lsr_kmeans_update(const float* x, const int32_t* assign, int64_t M, int D, i
     if (!x || !assign || !workspace || !centers_out || !counts_out) return LSR_EINVAL;
     if (misaligned16(workspace) || misaligned16(centers_out)) return LSR_EINVAL;
     LSR_HIP(launch_kmeans_update(x, assign, (int)M, D, K, workspace, centers_out, counts_out, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+size_t lsr_mask_nms_workspace_bytes(int N) { return N < 0 || N > LSR_MASK_MAX_N ? 0 : mask_nms_workspace_bytes(N); }
+
+int lsr_mask_pack(const uint8_t* masks, int N, int H, int W, uint64_t* words, int32_t* area, void* stream)
+{
+    LSR_TRY(mask_args(N, H, W));
+    if (N == 0) return LSR_OK;
+    if (!masks || !words || !area || misaligned(words, 8) || misaligned(area, 4)) return LSR_EINVAL;
+    LSR_HIP(launch_mask_pack(masks, N, H * W, (unsigned long long*)words, area, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_mask_pair_counts(const uint64_t* words, int N, int H, int W, const int32_t* order, int32_t* inter,
+                         void* stream)
+{
+    LSR_TRY(mask_args(N, H, W));
+    if (N == 0) return LSR_OK;
+    if (!words || !inter || misaligned(words, 8) || misaligned(order, 4) || misaligned(inter, 4)) return LSR_EINVAL;
+    LSR_HIP(launch_mask_pairs((const unsigned long long*)words, N, (H * W + 63) / 64, order, inter,
+                              (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_mask_nms_select(const uint64_t* words, const int32_t* area, int N, int H, int W, const int32_t* order,
+                        const uint8_t* conf, double iou_thr, double inner_thr, void* workspace, uint8_t* keep,
+                        uint8_t* criteria, int64_t* selected, int32_t* count, void* stream)
+{
+    LSR_TRY(mask_args(N, H, W));
+    if (N == 0) return LSR_OK;
+    if (!words || !area || !order || !conf || !workspace || !keep || !selected || !count) return LSR_EINVAL;
+    if (misaligned(words, 8) || misaligned(area, 4) || misaligned(order, 4) || misaligned(workspace, 16) ||
+        misaligned(selected, 8) || misaligned(count, 4))
+        return LSR_EINVAL;
+    LSR_HIP(launch_mask_pairs((const unsigned long long*)words, N, (H * W + 63) / 64, order, (int*)workspace,
+                              (hipStream_t)stream));
+    // torch compares a float32 tensor with a Python scalar in float32; 1 - inner_thr is a Python double first
+    LSR_HIP(launch_mask_decide(area, N, order, conf, (float)iou_thr, (float)(1.0 - inner_thr), workspace, keep,
+                               criteria, (long long*)selected, count, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_mask_segmaps(const uint64_t* const* words, const int32_t* const* kept, const int32_t* masks,
+                     const int32_t* counts, const int32_t* offsets, int H, int W, int index_type, void* out,
+                     void* stream)
+{
+    LSR_TRY(mask_args(0, H, W));
+    if (!words || !kept || !masks || !counts || !offsets || !out || misaligned(out, 4)) return LSR_EINVAL;
+    if (index_type != LSR_INDEX_F32 && index_type != LSR_INDEX_I32) return LSR_EINVAL;
+    for (int l = 0; l < 4; ++l) {
+        if (masks[l] < 0 || counts[l] < 0 || offsets[l] < 0) return LSR_EINVAL;
+        if (masks[l] > LSR_MASK_MAX_N || counts[l] > LSR_MASK_MAX_N) return LSR_EUNSUPPORTED;
+        if (counts[l] > 0 && (!words[l] || !kept[l] || misaligned(words[l], 8) || misaligned(kept[l], 4)))
+            return LSR_EINVAL;
+    }
+    LSR_HIP(launch_mask_segmaps((const unsigned long long* const*)words, kept, masks, counts, offsets, H * W,
+                                index_type == LSR_INDEX_I32, out, (hipStream_t)stream));
     return LSR_OK;
 }
 

@@ -309,6 +309,20 @@ hipError_t launch_kmeans_assign(const float* x, int M, int D, int K, const void*
 hipError_t launch_kmeans_update(const float* x, const int* assign, int M, int D, int K, void* ws, float* centers_out,
                                 int* counts_out, hipStream_t st);
 
+// mask_nms.hip: SAM mask NMS and segment maps on bit-packed masks (N <= LSR_MASK_MAX_N, HW <= LSR_MASK_MAX_PIXELS)
+size_t mask_nms_workspace_bytes(int N);   // starts with the (N, N) int32 pair table
+hipError_t launch_mask_pack(const uint8_t* masks, int N, int HW, unsigned long long* words, int* area, hipStream_t st);
+// inter (N, N): |mask order[i] & mask order[j]| for i <= j, 0 below the diagonal
+hipError_t launch_mask_pairs(const unsigned long long* words, int N, int W64, const int* order, int* inter,
+                             hipStream_t st);
+// from the pair table at the start of ws: keep, criteria (or nullptr), selected, count
+hipError_t launch_mask_decide(const int* area, int N, const int* order, const uint8_t* conf, float iou_thr,
+                              float inner_cut, void* ws, uint8_t* keep, uint8_t* criteria, long long* selected,
+                              int* count, hipStream_t st);
+// out (4, HW) as int32 or fp32; the five arrays are host arrays of 4
+hipError_t launch_mask_segmaps(const unsigned long long* const* words, const int* const* kept, const int* masks,
+                               const int* counts, const int* offsets, int HW, bool as_int, void* out, hipStream_t st);
+
 // densify.hip: densify_and_prune as one gather (plan: classify, scan, fill; apply: all 18 tensors)
 struct DensifyArgs {
     float max_grad, dense_thresh, min_opacity, big_thresh;   // thresholds as the reference's fp32 comparisons see them

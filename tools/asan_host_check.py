@@ -102,6 +102,7 @@ OK, ENOMEM = 0, 4
 NOALLOC = L.ALLOC_FN()   # a NULL allocator
 ODD = P + 4              # a pointer that is not 16-B aligned
 NAN = float("nan")
+P4, I4 = ctypes.c_void_p * 4, ctypes.c_int32 * 4   # lsr_mask_segmaps' host arrays of four levels
 TABLE = [
     # lsr_quick_decode(wmap, cb, L, K, Df, H, W, normalize, eps, out, alloc, ctx, stream)
     ("lsr_quick_decode", (None, None, 3, 32, 500, 4, 4, 1, 1e-10, None, ALLOC, None, None), EINVAL),   # both
@@ -337,6 +338,51 @@ TABLE = [
     ("lsr_kmeans_update", (P, P, -1, 512, 64, P, P, P, None), EINVAL),
     ("lsr_kmeans_update", (None, None, 0, 6, 64, None, None, None, None), EINVAL),      # the shape before the no-op
     ("lsr_kmeans_update", (None, None, 0, 512, 64, None, None, None, None), OK),
+    # lsr_mask_pack(masks, N, H, W, words, area, stream): beyond 4096 masks or 2^24 pixels is unsupported
+    ("lsr_mask_pack", (None, 5, 3, 5, P, P, None), EINVAL),
+    ("lsr_mask_pack", (P, 5, 3, 5, None, P, None), EINVAL),
+    ("lsr_mask_pack", (P, 5, 3, 5, P, None, None), EINVAL),
+    ("lsr_mask_pack", (P, 5, 3, 5, ODD, P, None), EINVAL),
+    ("lsr_mask_pack", (P, -1, 3, 5, P, P, None), EINVAL),
+    ("lsr_mask_pack", (P, 5, 0, 5, P, P, None), EINVAL),
+    ("lsr_mask_pack", (P, 4097, 3, 5, P, P, None), EUNSUP),
+    ("lsr_mask_pack", (P, 5, 4096, 4097, P, P, None), EUNSUP),
+    ("lsr_mask_pack", (None, 4097, 0, 5, None, None, None), EINVAL),   # both
+    ("lsr_mask_pack", (None, 0, 0, 5, None, None, None), EINVAL),      # the shape before the no-op
+    ("lsr_mask_pack", (None, 0, 3, 5, None, None, None), OK),
+    # lsr_mask_pair_counts(words, N, H, W, order, inter, stream)
+    ("lsr_mask_pair_counts", (None, 5, 3, 5, None, P, None), EINVAL),
+    ("lsr_mask_pair_counts", (P, 5, 3, 5, None, None, None), EINVAL),
+    ("lsr_mask_pair_counts", (ODD, 5, 3, 5, None, P, None), EINVAL),
+    ("lsr_mask_pair_counts", (P, 4097, 3, 5, None, P, None), EUNSUP),
+    ("lsr_mask_pair_counts", (P, 5, 4096, 4097, None, P, None), EUNSUP),
+    ("lsr_mask_pair_counts", (None, 0, 3, 5, None, None, None), OK),
+    # lsr_mask_nms_select(words, area, N, H, W, order, conf, iou_thr, inner_thr, workspace, keep, criteria,
+    #                     selected, count, stream)
+    ("lsr_mask_nms_select", (None, P, 5, 3, 5, P, P, 0.8, 0.5, P, P, None, P, P, None), EINVAL),
+    ("lsr_mask_nms_select", (P, None, 5, 3, 5, P, P, 0.8, 0.5, P, P, None, P, P, None), EINVAL),
+    ("lsr_mask_nms_select", (P, P, 5, 3, 5, None, P, 0.8, 0.5, P, P, None, P, P, None), EINVAL),
+    ("lsr_mask_nms_select", (P, P, 5, 3, 5, P, None, 0.8, 0.5, P, P, None, P, P, None), EINVAL),
+    ("lsr_mask_nms_select", (P, P, 5, 3, 5, P, P, 0.8, 0.5, None, P, None, P, P, None), EINVAL),
+    ("lsr_mask_nms_select", (P, P, 5, 3, 5, P, P, 0.8, 0.5, ODD, P, None, P, P, None), EINVAL),
+    ("lsr_mask_nms_select", (P, P, 5, 3, 5, P, P, 0.8, 0.5, P, None, None, P, P, None), EINVAL),
+    ("lsr_mask_nms_select", (P, P, 5, 3, 5, P, P, 0.8, 0.5, P, P, None, None, P, None), EINVAL),
+    ("lsr_mask_nms_select", (P, P, 5, 3, 5, P, P, 0.8, 0.5, P, P, None, P, None, None), EINVAL),
+    ("lsr_mask_nms_select", (P, P, -1, 3, 5, P, P, 0.8, 0.5, P, P, None, P, P, None), EINVAL),
+    ("lsr_mask_nms_select", (P, P, 4097, 3, 5, P, P, 0.8, 0.5, P, P, None, P, P, None), EUNSUP),
+    ("lsr_mask_nms_select", (P, P, 5, 4096, 4097, P, P, 0.8, 0.5, P, P, None, P, P, None), EUNSUP),
+    ("lsr_mask_nms_select", (None, None, 0, 3, 5, None, None, 0.8, 0.5, None, None, None, None, None, None), OK),
+    # lsr_mask_segmaps(words[4], kept[4], masks[4], counts[4], offsets[4], H, W, index_type, out, stream)
+    ("lsr_mask_segmaps", (None, P4(), I4(), I4(), I4(), 3, 5, 0, P, None), EINVAL),
+    ("lsr_mask_segmaps", (P4(), P4(), I4(), I4(), I4(), 3, 5, 0, None, None), EINVAL),
+    ("lsr_mask_segmaps", (P4(), P4(), I4(), I4(), I4(), 3, 5, 2, P, None), EINVAL),
+    ("lsr_mask_segmaps", (P4(), P4(), I4(), I4(), I4(), 0, 5, 0, P, None), EINVAL),
+    ("lsr_mask_segmaps", (P4(), P4(), I4(), I4(), I4(), 4096, 4097, 0, P, None), EUNSUP),
+    ("lsr_mask_segmaps", (P4(), P4(), I4(2), I4(1), I4(), 3, 5, 0, P, None), EINVAL),       # a counted level without pointers
+    ("lsr_mask_segmaps", (P4(P), P4(P), I4(2), I4(-1), I4(), 3, 5, 0, P, None), EINVAL),
+    ("lsr_mask_segmaps", (P4(P), P4(P), I4(2), I4(1), I4(-1), 3, 5, 0, P, None), EINVAL),
+    ("lsr_mask_segmaps", (P4(P), P4(P), I4(2), I4(4097), I4(), 3, 5, 0, P, None), EUNSUP),
+    ("lsr_mask_segmaps", (P4(P), P4(P), I4(4097), I4(1), I4(), 3, 5, 0, P, None), EUNSUP),
 ]
 for fn, args, want in TABLE:
     rc = getattr(lib, fn)(*args)
@@ -359,6 +405,9 @@ for args, some in [((3, 64, 512, 0), True), ((-1, 64, 512, 1), False), ((3, 64, 
 for args, some in [((1000, 64, 512), True), ((0, 1, 4), True), ((10, 0, 512), False), ((10, 257, 512), False),
                    ((10, 64, 6), False), ((10, 64, 1028), False), ((-1, 64, 512), False), ((1 << 31, 64, 512), False)]:
     assert (lib.lsr_kmeans_workspace_bytes(*args) > 0) == some, args
+    calls += 1
+for n, some in [(1, True), (0, True), (4096, True), (-1, False), (4097, False)]:
+    assert (lib.lsr_mask_nms_workspace_bytes(n) > 0) == some, n
     calls += 1
 for args, some in [((2, 4, 4), True), ((0, 4, 4), False), ((2, 0, 4), False), ((-1, 4, 4), False), ((70000, 4, 4), False)]:
     assert (lib.lsr_query_post_workspace_bytes(*args) > 0) == some, args
