@@ -13,6 +13,9 @@
 #ifndef LSR_BWD16_WAVES
 #define LSR_BWD16_WAVES 4  // the headline D = 16 list-driven backward: waves per SIMD it is compiled for
 #endif
+#ifndef LSR_BWD_LD_STATIC
+#define LSR_BWD_LD_STATIC 1  // direct-dL/dlang kernels: compile-time row strides, buffer atomics only (BA below)
+#endif
 #ifndef LSR_MF_WAVES
 #define LSR_MF_WAVES 2      // MFMA render kernels: min waves per SIMD (caps VGPRs at 256)
 #endif
@@ -327,9 +330,14 @@ __device__ __forceinline__ void dot_features(const RenderArgs& a, uint32_t gid, 
 // chunk ahead.  The same candidates in the same order: results unchanged.
 // DET: the per-block partials are added as 64-bit fixed-point integers
 // (render_det.h: det_add at det_shift's exponents) instead of float atomics.
-template <int NL, bool LO = false, bool LD = false, bool SP = false, bool LST = false, bool DET = false>
+// BA (with LD, not DET: the headline's kernel): the launcher has checked that
+// every gradient byte offset fits the buffer atomics' 31 bits, so the 64-bit
+// global-atomic fallback is not compiled into the group loop.  LD's row
+// strides (VP = 16, D = NL) are compile-time constants: shifts and adds.
+template <int NL, bool LO = false, bool LD = false, bool SP = false, bool LST = false, bool DET = false, bool BA = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bwd_waves<NL, LD, LST, DET>()))) k_render_bwd_mf(RenderBwdArgs b)
 {
+    static_assert(!BA || (LD && !DET), "BA: the direct-dL/dlang float-atomic backward");
     static_assert(!(LST && SP), "the sparse-input backward follows the quick forward (no lists)");
     static_assert(!(DET && SP), "the deterministic backward expands the sparse input (lsr_api backward_quick)");
     static_assert(!LO || NL > 0, "language-only backward needs D > 0");
@@ -384,14 +392,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bwd_wav
     const uint32_t rs = wt.ent ? wt.rs : a.tile_start[wt.tile];
     const size_t HW = (size_t)c.H * c.W;
     const size_t pix = (size_t)pm.py * c.W + pm.px;
-    const int D = a.D;
-    const int VP = b.VP;
+    // LD: D == NL (launch_render_bwd) and 16-value rows (plan_backward)
+    const int D = (LD && LSR_BWD_LD_STATIC) ? NL : a.D;
+    const int VP = (LD && LSR_BWD_LD_STATIC) ? 16 : b.VP;
     const float ddelx_dx = 0.5f * (float)c.W, ddely_dy = 0.5f * (float)c.H;
     // gradient rows (and LD: the language output) as raw buffers when every
     // byte offset fits 31 bits (uniform; otherwise 64-bit global atomics)
     const uint64_t nbg = (uint64_t)a.P * (uint64_t)VP * 4u;
     const uint64_t nbl = LD ? (uint64_t)a.P * (uint64_t)D * 4u : 0u;
-    const bool buf_atom = nbg < (uint64_t)LSR_BUF_OOB && nbl < (uint64_t)LSR_BUF_OOB;
+    const bool buf_atom = BA || (nbg < (uint64_t)LSR_BUF_OOB && nbl < (uint64_t)LSR_BUF_OOB);
     const __amdgpu_buffer_rsrc_t rg =
         __builtin_amdgcn_make_buffer_rsrc(b.grad_acc, 0, (int)min(nbg, (uint64_t)LSR_BUF_OOB), 0x00020000);
     const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(
@@ -914,7 +923,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bwd_wav
                             }
                         }
                     }
-                } else
+                } else if constexpr (!BA)
 #pragma unroll
                 for (int h = 0; h < GRL; h++) {
                     const int f = 16 * h + li;
@@ -999,11 +1008,18 @@ hipError_t launch_render_bwd(const RenderBwdArgs& b, hipStream_t st)
     const bool ld = b.lang_acc != nullptr;   // LD: dL/dlanguage straight into lang_acc (then D == NL)
     if (det && (!b.det_bounds || !b.det_sh || (ld != (b.det_lang != nullptr)))) return hipErrorInvalidValue;
     if (ld && (!bwd_lang_direct(b.f.D) || (uintptr_t)b.f.lang % 16 != 0)) return hipErrorInvalidValue;
+    if (ld && LSR_BWD_LD_STATIC && b.VP != 16) return hipErrorInvalidValue;   // the kernel's compile-time row width
     BwdKernel k = nullptr;
     const bool known = with_lang_set(lang_set_for(b.f.D), [&](auto nl) {
         constexpr int NL = decltype(nl)::value;
         with_bools([&](auto ldc, auto lstc, auto detc) {
-            if constexpr (!ldc.value || lang_direct_set(NL))
+            if constexpr (ldc.value && !detc.value && LSR_BWD_LD_STATIC) {
+                // LD: (P, 16) rows and (P, NL) language rows; BA when both fit the buffer atomics' offsets
+                const uint64_t nb = (uint64_t)b.f.P * (uint64_t)(NL > 16 ? NL : 16) * 4u;
+                if constexpr (lang_direct_set(NL))
+                    k = nb < (uint64_t)LSR_BUF_OOB ? k_render_bwd_mf<NL, false, true, false, lstc.value, false, true>
+                                                   : k_render_bwd_mf<NL, false, true, false, lstc.value, false>;
+            } else if constexpr (!ldc.value || lang_direct_set(NL))
                 k = k_render_bwd_mf<NL, false, ldc.value, false, lstc.value, detc.value>;
         }, ld, lst, det);
     });

@@ -3,7 +3,45 @@
 // Work decomposition: render_common.h.
 #include "render_common.h"
 
+// The ML blend loop's issue-slot cuts; each is bit-identical to
+// its 0 form and can be built out for an A/B (make variant VFLAGS=-DLSR_FWD_..=0).
+#ifndef LSR_FWD_EXP4
+#define LSR_FWD_EXP4 1   // a group's two packed exponent chains advance in lockstep
+#endif
+#ifndef LSR_FWD_RGB
+#define LSR_FWD_RGB 1    // 16-B RGB reads, scalar (not SLP-packed) RGB accumulation
+#endif
+
 namespace lsr {
+
+// expf_det2 (lsr_device.h) of two pairs, statement by statement in lockstep:
+// the same operations per half in the same order (bitwise expf_det2), with
+// every packed FMA followed by an independent one instead of its dependant.
+__device__ __forceinline__ void expf_det2x2(f32x2 x0, f32x2 x1, f32x2& e0, f32x2& e1)
+{
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    auto fma2 = [](f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); };
+    auto k2 = [](float v) { return f32x2{v, v}; };
+    x0 = f32x2{__builtin_amdgcn_fmed3f(x0.x, -87.0f, 1.0e30f), __builtin_amdgcn_fmed3f(x0.y, -87.0f, 1.0e30f)};
+    x1 = f32x2{__builtin_amdgcn_fmed3f(x1.x, -87.0f, 1.0e30f), __builtin_amdgcn_fmed3f(x1.y, -87.0f, 1.0e30f)};
+    const f32x2 t0 = fma2(x0, k2(1.44269504088896341f), k2(12582912.0f));
+    const f32x2 t1 = fma2(x1, k2(1.44269504088896341f), k2(12582912.0f));
+    const f32x2 n0 = t0 - k2(12582912.0f), n1 = t1 - k2(12582912.0f);
+    f32x2 r0 = fma2(n0, k2(-0.693145751953125f), x0), r1 = fma2(n1, k2(-0.693145751953125f), x1);
+    r0 = fma2(n0, k2(-1.428606765330187e-06f), r0);
+    r1 = fma2(n1, k2(-1.428606765330187e-06f), r1);
+    f32x2 p0 = k2(0x1.6aea1ap-10f), p1 = p0;
+    constexpr float cf[6] = {0x1.1267d2p-7f, 0x1.555820p-5f, 0x1.555418p-3f, 0x1.fffffcp-2f, 1.0f, 1.0f};
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        p0 = fma2(p0, r0, k2(cf[i]));
+        p1 = fma2(p1, r1, k2(cf[i]));
+    }
+    const u32x2 s0 = (__builtin_bit_cast(u32x2, t0) << 23) + u32x2{0x3f800000u, 0x3f800000u};
+    const u32x2 s1 = (__builtin_bit_cast(u32x2, t1) << 23) + u32x2{0x3f800000u, 0x3f800000u};
+    e0 = p0 * __builtin_bit_cast(f32x2, s0);
+    e1 = p1 * __builtin_bit_cast(f32x2, s1);
+}
 
 // Stage one instance's feature row (rgb + dense language) into LDS.
 template <int NL, int F4>
@@ -293,6 +331,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fwd_wav
                 // exponent <= 0, alpha >= 1/255), else 0; cm[k] the lanes of al != 0
                 float al[4];
                 bool cm[4];
+                f32x2 EX4[2];
+                (void)EX4;
+                if constexpr (LSR_FWD_EXP4) {
+                    f32x2 P4[2];
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        const int e = (q0 >> 1) + h;
+                        const f32x2 dx = st.X[e] - f32x2{pfx, pfx}, dy = st.Y[e] - f32x2{pfy, pfy};
+                        P4[h] = __builtin_elementwise_fma(f32x2{-0.5f, -0.5f},
+                                                          __builtin_elementwise_fma(st.CA[e] * dx, dx, (st.CC[e] * dy) * dy),
+                                                          -((st.CB[e] * dx) * dy));
+                    }
+                    expf_det2x2(P4[0], P4[1], EX4[0], EX4[1]);
+                }
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     const int j0 = q0 + 2 * h, e = j0 >> 1;
@@ -302,7 +354,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fwd_wav
                     const f32x2 P = __builtin_elementwise_fma(f32x2{-0.5f, -0.5f},
                                                               __builtin_elementwise_fma(sCA * dx, dx, (sCC * dy) * dy),
                                                               -((sCB * dx) * dy));
-                    const f32x2 EX = expf_det2(P);
+                    const f32x2 EX = LSR_FWD_EXP4 ? EX4[h] : expf_det2(P);
                     const float a0 = fminf(0.99f, OP.x * EX.x), a1 = fminf(0.99f, OP.y * EX.y);
                     // no exponent-cut test: below the cut the 1/255 test rejects the pair
                     const bool c0 = (j0 < n) & !done & !(P.x > 0.0f) & !(a0 < 1.0f / 255.0f);
@@ -324,6 +376,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fwd_wav
                     const int kk = min(q0 + k, n - 1);
                     if constexpr (SF) {   // the line staged with the candidate
                         const float4 f = st.R[kk];
+                        // keep the 16-B read (ds_read_b128: 4 LDS cycles, the narrowed b96: 8)
+                        if constexpr (LSR_FWD_RGB) asm volatile("" ::"v"(f.w));
                         return make_float3(f.x, f.y, f.z);
                     } else {
                         const float4 f = st.F[kk * F4];
@@ -343,6 +397,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fwd_wav
                         acc[0] = fmaf(f.x, aT, acc[0]);
                         acc[1] = fmaf(f.y, aT, acc[1]);
                         acc[2] = fmaf(f.z, aT, acc[2]);
+                        // three scalar chains: packed into v_pk_fma_f32 they need register
+                        // shuffles, and packed f32 beside the MFMAs costs more than it saves
+                        if constexpr (LSR_FWD_RGB) asm("" : "+v"(acc[1]), "+v"(acc[2]));
                         lastj = cm[k] ? q0 + k : lastj;
                         s4[k] = aT;
                     }

@@ -1,4 +1,4 @@
-"""Instruction mix of the innermost loops of a kernel in a hipcc .s file
+"""Instruction mix (VALU, MFMA, SALU, s_nop, LDS, VMEM) of the loops of a kernel in a hipcc .s file
 (blocks LLVM annotates as belonging to the loop).
 Usage: python tools/loop_stats.py FILE.s KERNEL_SYMBOL"""
 import collections
@@ -37,8 +37,9 @@ def main():
         cat = collections.Counter()
         for blk in ins:
             for op in blk:
-                cat["valu" if op.startswith("v_") else "salu" if op.startswith("s_") else "lds" if op.startswith(
-                    "ds_") else "vmem" if op.startswith(("global_", "buffer_")) else op] += 1
+                cat["mfma" if op.startswith("v_mfma") else "valu" if op.startswith("v_") else "nop" if op == "s_nop"
+                    else "salu" if op.startswith("s_") else "lds" if op.startswith("ds_")
+                    else "vmem" if op.startswith(("global_", "buffer_")) else op] += 1
         print(f"loop {lp} depth {d}: {sum(cat.values())} instructions {dict(cat)}")
 
 
