@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_mask_nms_workspace_bytes, lsr_mask_pack / _pair_counts / _nms_select / _segmaps;
+#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_mask_boxes, lsr_clip_tiles;
+                               12, additive (no bump): lsr_mask_nms_workspace_bytes, lsr_mask_pack / _pair_counts / _nms_select / _segmaps;
                                12, additive (no bump): lsr_kmeans_workspace_bytes / _prepare / _assign / _update;
                                12, additive (no bump): lsr_photo_loss_forward / _backward;
                                12, additive (no bump): lsr_quick_heat_plan_bytes / _prepare / _run, lsr_heat_frame;
@@ -538,6 +539,43 @@ int lsr_mask_nms_select(const uint64_t* words, const int32_t* area, int N, int H
 int lsr_mask_segmaps(const uint64_t* const* words, const int32_t* const* kept, const int32_t* masks,
                      const int32_t* counts, const int32_t* offsets, int H, int W, int index_type, void* out,
                      void* stream);
+
+/* The CLIP input tiles of the kept masks: mask2segmap's get_seg_img, pad_img and
+ * cv2.resize per mask (preprocess.py:304-317, :191-206), the / 255 of :315 and
+ * encode_image's normalisation and cast (:105-107), from the packed masks.
+ *
+ * lsr_mask_boxes writes boxes (N, 4) int32 x, y, w, h: the tight extents of each
+ * packed mask (w = xmax - x + 1, h = ymax - y + 1; an empty mask: 0, 0, 0, 0).
+ * lsr_clip_tiles writes n tiles of S x S pixels; tile t is mask keep[t] (keep
+ * NULL: mask t, and n <= N).  image is (H, W, 3) uint8, boxes (N, 4) int32 is
+ * indexed by mask.  Per tile, all in integers (DESIGN "CLIP tiles"):
+ *   crop   x0 = clamp(x, 0, W), x1 = clamp(x + w, 0, W), cw = max(x1 - x0, 0), likewise y0, ch;
+ *   pad    to a square of side l = max(cw, ch), the crop centred along its shorter side
+ *          (offset |ch - cw| / 2, rounded down); a pixel outside the crop or with its mask
+ *          bit clear is (0, 0, 0);
+ *   resize l x l -> S x S as OpenCV's 8-bit INTER_LINEAR: source coordinate
+ *          f = (float)((d + 0.5) * (1.0 / ((double)S / l)) - 0.5), 11-bit coefficients
+ *          rint(f * 2048), out = (((b0 (H0 >> 4)) >> 16) + ((b1 (H1 >> 4)) >> 16) + 2) >> 2.
+ * A tile with l = 0, or with a keep entry outside [0, N), is all zeros.
+ * out_type LSR_TILE_U8: out (n, S, S, 3) uint8, lut unused.  LSR_TILE_UNIT: out
+ * (n, 3, S, S) fp32 = lut[c][v], lut (3, 256) fp32.  LSR_TILE_CLIP: out
+ * (n, 3, S, S) fp16 = lut[c][v], lut (3, 256) fp16.  The caller fills lut (v / 255
+ * and its normalised form); the kernel does no float arithmetic on pixels.
+ *
+ * LSR_EINVAL, before any device call: N or n outside 0 .. LSR_MASK_MAX_N, H or
+ * W < 1 or H W > LSR_MASK_MAX_PIXELS, S outside 1 .. LSR_TILE_MAX_SIDE, an unknown
+ * out_type, keep NULL with n > N, a NULL or misaligned (words: 8 B; boxes, keep:
+ * 4 B; lut, fp32 / fp16 out: their element) pointer, lut NULL for a float form.
+ * N = 0 (boxes) and n = 0 (tiles): LSR_OK, nothing is read or written.  Additive
+ * to ABI 12. */
+#define LSR_TILE_MAX_SIDE 1024
+#define LSR_TILE_U8 0
+#define LSR_TILE_UNIT 1
+#define LSR_TILE_CLIP 2
+int lsr_mask_boxes(const uint64_t* words, int N, int H, int W, int32_t* boxes, void* stream);
+int lsr_clip_tiles(const uint8_t* image, int H, int W, const uint64_t* words, int N,
+                   const int32_t* keep /* or NULL */, const int32_t* boxes, int n, int S,
+                   const void* lut /* NULL for LSR_TILE_U8 */, int out_type, void* out, void* stream);
 
 /* Fused Adam step: the update of torch.optim.Adam as the
  * reference builds it (scene/gaussian_model.py:234-255, no amsgrad), one pass

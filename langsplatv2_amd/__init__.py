@@ -7,6 +7,7 @@ gaussian_renderer/__init__.py and train.py run unchanged.  Compute is in
 liblsr.so (C ABI: include/lsr.h).
 """
 from ._lib import deterministic, set_deterministic  # noqa: F401
+from .clip_tiles import clip_tiles, mask2segmap, mask_boxes, segment_tiles_and_maps  # noqa: F401
 from .codebook_init import (ResidualVectorQuantizationWithClustering, assign_codes, fit_codebooks,  # noqa: F401
                             kmeans_step, quantize)
 from .densify import (DensifyResult, densify_and_prune, densify_and_prune_torch, densify_tensors,  # noqa: F401
@@ -29,4 +30,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "photometric_loss", "l1_ssim", "densify_tensors", "densify_and_prune", "densify_and_prune_torch", "reset_opacity",
            "DensifyResult", "assign_codes", "kmeans_step", "quantize", "fit_codebooks",
            "ResidualVectorQuantizationWithClustering", "pack_masks", "mask_pair_counts", "mask_nms", "masks_update",
-           "build_seg_maps", "PackedMasks", "NmsResult"]
+           "build_seg_maps", "PackedMasks", "NmsResult", "mask_boxes", "clip_tiles", "mask2segmap",
+           "segment_tiles_and_maps"]

@@ -25,6 +25,7 @@ LSR_LAYOUT_CHW, LSR_LAYOUT_HWC = 0, 1
 LSR_QUERY_RELEVANCY, LSR_QUERY_COSINE = 0, 1
 LSR_HEAT_SUMMED_COSINE, LSR_HEAT_MEAN_RELEVANCY = 0, 1
 LSR_CURVE_UPPER_HALF, LSR_CURVE_POWER4 = 0, 1
+LSR_TILE_U8, LSR_TILE_UNIT, LSR_TILE_CLIP = 0, 1, 2
 
 _vp = ctypes.c_void_p
 
@@ -136,7 +137,7 @@ EXPORTS = ("lsr_forward", "lsr_backward", "lsr_mark_visible", "lsr_quick_decode"
            "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_photo_loss_forward", "lsr_photo_loss_backward",
            "lsr_kmeans_workspace_bytes", "lsr_kmeans_prepare", "lsr_kmeans_assign", "lsr_kmeans_update",
            "lsr_mask_nms_workspace_bytes", "lsr_mask_pack", "lsr_mask_pair_counts", "lsr_mask_nms_select",
-           "lsr_mask_segmaps",
+           "lsr_mask_segmaps", "lsr_mask_boxes", "lsr_clip_tiles",
            "lsr_densify_workspace_bytes", "lsr_densify_plan", "lsr_densify_apply", "lsr_reset_opacity", "lsr_adam_step", "lsr_sh_grad_from_views", "lsr_strerror",
            "lsr_abi_version", "lsr_max_lang_dim", "lsr_profile_enable", "lsr_profile_stages", "lsr_profile_reset",
            "lsr_profile_query", "lsr_set_option", "lsr_get_option", "lsr_stream_create", "lsr_stream_destroy")
@@ -245,6 +246,10 @@ def load(path: str | None = None):
     lib.lsr_mask_nms_select.restype = ctypes.c_int
     lib.lsr_mask_segmaps.argtypes = [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp]
     lib.lsr_mask_segmaps.restype = ctypes.c_int
+    lib.lsr_mask_boxes.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp]
+    lib.lsr_mask_boxes.restype = ctypes.c_int
+    lib.lsr_clip_tiles.argtypes = [_vp, _ci, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _vp]
+    lib.lsr_clip_tiles.restype = ctypes.c_int
     lib.lsr_densify_workspace_bytes.argtypes = [_i64]
     lib.lsr_densify_workspace_bytes.restype = ctypes.c_size_t
     lib.lsr_densify_plan.argtypes = [_i64, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _ci, _cf, _vp,

@@ -63,6 +63,15 @@ int mask_args(int N, int H, int W)
 
 bool misaligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
+// the tile entry points take the mask kernels' limits and call everything beyond them invalid
+int tile_args(int N, int n, int H, int W, int S)
+{
+    if (N < 0 || N > LSR_MASK_MAX_N || n < 0 || n > LSR_MASK_MAX_N || H < 1 || W < 1 ||
+        (int64_t)H * W > LSR_MASK_MAX_PIXELS || S < 1 || S > LSR_TILE_MAX_SIDE)
+        return LSR_EINVAL;
+    return LSR_OK;
+}
+
 // a code count the kernels are not built for is unsupported, anything else invalid
 int topk_code_args(int64_t N, int L, int K, int k)
 {
@@ -401,6 +410,32 @@ int lsr_mask_segmaps(const uint64_t* const* words, const int32_t* const* kept, c
     }
     LSR_HIP(launch_mask_segmaps((const unsigned long long* const*)words, kept, masks, counts, offsets, H * W,
                                 index_type == LSR_INDEX_I32, out, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_mask_boxes(const uint64_t* words, int N, int H, int W, int32_t* boxes, void* stream)
+{
+    if (tile_args(N, 0, H, W, 1) != LSR_OK) return LSR_EINVAL;
+    if (N == 0) return LSR_OK;
+    if (!words || !boxes || misaligned(words, 8) || misaligned(boxes, 4)) return LSR_EINVAL;
+    LSR_HIP(launch_mask_boxes((const unsigned long long*)words, N, H, W, boxes, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_clip_tiles(const uint8_t* image, int H, int W, const uint64_t* words, int N, const int32_t* keep,
+                   const int32_t* boxes, int n, int S, const void* lut, int out_type, void* out, void* stream)
+{
+    LSR_TRY(tile_args(N, n, H, W, S));
+    if (out_type != LSR_TILE_U8 && out_type != LSR_TILE_UNIT && out_type != LSR_TILE_CLIP) return LSR_EINVAL;
+    if (!keep && n > N) return LSR_EINVAL;
+    if (n == 0) return LSR_OK;
+    if (!image || !words || !boxes || !out || (out_type != LSR_TILE_U8 && !lut)) return LSR_EINVAL;
+    const uintptr_t elem = out_type == LSR_TILE_UNIT ? 4 : out_type == LSR_TILE_CLIP ? 2 : 1;
+    if (misaligned(words, 8) || misaligned(boxes, 4) || misaligned(keep, 4) || misaligned(lut, elem) ||
+        misaligned(out, elem))
+        return LSR_EINVAL;
+    LSR_HIP(launch_clip_tiles(image, H, W, (const unsigned long long*)words, N, keep, boxes, n, S, lut, out_type, out,
+                              (hipStream_t)stream));
     return LSR_OK;
 }
 

@@ -323,6 +323,13 @@ hipError_t launch_mask_decide(const int* area, int N, const int* order, const ui
 hipError_t launch_mask_segmaps(const unsigned long long* const* words, const int* const* kept, const int* masks,
                                const int* counts, const int* offsets, int HW, bool as_int, void* out, hipStream_t st);
 
+// clip_tiles.hip: tight boxes of packed masks; the S x S CLIP tiles of n of them (S <= LSR_TILE_MAX_SIDE)
+hipError_t launch_mask_boxes(const unsigned long long* words, int N, int H, int W, int* boxes, hipStream_t st);
+// out: (n, S, S, 3) uint8 (LSR_TILE_U8) or (n, 3, S, S) through lut (3, 256), fp32 (_UNIT) or fp16 (_CLIP)
+hipError_t launch_clip_tiles(const uint8_t* image, int H, int W, const unsigned long long* words, int N,
+                             const int* keep, const int* boxes, int n, int S, const void* lut, int out_type, void* out,
+                             hipStream_t st);
+
 // densify.hip: densify_and_prune as one gather (plan: classify, scan, fill; apply: all 18 tensors)
 struct DensifyArgs {
     float max_grad, dense_thresh, min_opacity, big_thresh;   // thresholds as the reference's fp32 comparisons see them

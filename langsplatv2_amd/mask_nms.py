@@ -14,8 +14,9 @@ that `lang_loss.language_gt_index` reads.  Here the masks are bit-packed once
 popcount(a & b), the decision is one launch with no host read-back, the segment
 maps one thread per pixel.  The float arithmetic is the reference's, quirks
 included (DESIGN, "Mask NMS and segment maps"); ties in the scores keep input
-order (a stable sort).  SAM and OpenCLIP themselves, and the 224 x 224 CLIP
-tiles, are not part of this.  There is no CPU path.
+order (a stable sort).  The 224 x 224 CLIP tiles of the kept masks are cut from
+the same packed masks by clip_tiles.py; SAM and OpenCLIP themselves are not
+part of this.  There is no CPU path.
 """
 from __future__ import annotations
 

@@ -383,6 +383,33 @@ TABLE = [
     ("lsr_mask_segmaps", (P4(P), P4(P), I4(2), I4(1), I4(-1), 3, 5, 0, P, None), EINVAL),
     ("lsr_mask_segmaps", (P4(P), P4(P), I4(2), I4(4097), I4(), 3, 5, 0, P, None), EUNSUP),
     ("lsr_mask_segmaps", (P4(P), P4(P), I4(4097), I4(1), I4(), 3, 5, 0, P, None), EUNSUP),
+    # lsr_mask_boxes(words, N, H, W, boxes, stream): every rejected argument is invalid
+    ("lsr_mask_boxes", (None, 5, 3, 5, P, None), EINVAL),
+    ("lsr_mask_boxes", (P, 5, 3, 5, None, None), EINVAL),
+    ("lsr_mask_boxes", (ODD, 5, 3, 5, P, None), EINVAL),
+    ("lsr_mask_boxes", (P, 4097, 3, 5, P, None), EINVAL),
+    ("lsr_mask_boxes", (P, 5, 4096, 4097, P, None), EINVAL),
+    ("lsr_mask_boxes", (None, 0, 0, 5, None, None), EINVAL),      # the shape before the no-op
+    ("lsr_mask_boxes", (None, 0, 3, 5, None, None), OK),
+    # lsr_clip_tiles(image, H, W, words, N, keep, boxes, n, S, lut, out_type, out, stream)
+    ("lsr_clip_tiles", (None, 3, 5, P, 5, P, P, 4, 224, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, None, 5, P, P, 4, 224, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, None, 4, 224, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, P, 4, 224, P, 2, None, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, P, 4, 224, None, 2, P, None), EINVAL),    # a float form without its table
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, P, 4, 224, None, 1, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, None, P, 6, 224, P, 2, P, None), EINVAL),    # no keep: n <= N
+    ("lsr_clip_tiles", (P, 3, 5, P, 4097, P, P, 4, 224, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, P, 4097, 224, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, P, -1, 224, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 4096, 4097, P, 5, P, P, 4, 224, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, P, 4, 0, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, P, 4, 1025, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, P, 4, 224, P, 3, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, ODD, 5, P, P, 4, 224, P, 2, P, None), EINVAL),
+    ("lsr_clip_tiles", (P, 3, 5, P, 5, P, P, 4, 224, P, 1, P + 2, None), EINVAL),   # fp32 tiles on a 2-B boundary
+    ("lsr_clip_tiles", (None, 0, 5, None, 5, None, None, 0, 224, None, 2, None, None), EINVAL),   # the shape first
+    ("lsr_clip_tiles", (None, 3, 5, None, 5, None, None, 0, 224, None, 2, None, None), OK),
 ]
 for fn, args, want in TABLE:
     rc = getattr(lib, fn)(*args)
