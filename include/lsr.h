@@ -428,6 +428,29 @@ int lsr_lang_loss_backward(const float* weight_map, const float* codebooks, int 
                            const float* grad_loss, float* grad_weight_map, float* grad_codebooks, lsr_alloc_fn alloc,
                            void* alloc_ctx, void* stream);
 
+/* L1 loss of the same step (train.py:157-167 with --l1_loss; normalize != 0
+ * is --normalize), same tensors, limits and masking rule as the cosine pair:
+ *   u_p  = f_p, or f_p / (|f_p| + 1e-10) with normalize
+ *   loss = mean over all Df*H*W elements of mask_p |u_pd - gt_pd|
+ *                                        l1_loss, utils/loss_utils.py:18-19
+ * Nothing of size Df x pixels is materialised: f is formed 16 features x 64
+ * pixels at a time on the exact-f32 matrix units and compared in registers.
+ * The loss is summed in a fixed order (bit-identical from run to run).
+ * Forward writes loss[0] and, with normalize, pixel_stats (2, H, W) (|f_p|
+ * and sum_d u_pd sign(u_pd - gt_pd)); either may be NULL, and without
+ * normalize pixel_stats is neither written nor read.  Backward writes
+ * grad_weight_map (K, H, W) and grad_codebooks (K, Df), both scaled by the
+ * device scalar *grad_loss, with sign(0) = 0 and the norm's zero subgradient
+ * at |f_p| = 0, from the forward's pixel_stats (NULL: recomputed).
+ * Workspace via alloc (LSR_BUF_LOSS). */
+int lsr_lang_l1_forward(const float* weight_map, const float* codebooks, int K, int Df, int H, int W,
+                        const int32_t* seg, const float* features, int S, int normalize, float* loss,
+                        float* pixel_stats, lsr_alloc_fn alloc, void* alloc_ctx, void* stream);
+int lsr_lang_l1_backward(const float* weight_map, const float* codebooks, int K, int Df, int H, int W,
+                         const int32_t* seg, const float* features, int S, int normalize, const float* pixel_stats,
+                         const float* grad_loss, float* grad_weight_map, float* grad_codebooks, lsr_alloc_fn alloc,
+                         void* alloc_ctx, void* stream);
+
 /* Photometric loss of the RGB training step (train.py:170-173,
  * utils/loss_utils.py:18-71): image and gt are planes = B*C contiguous fp32
  * planes of H x W.  Forward writes out[0] = mean |image - gt| and out[1] = mean

@@ -14,6 +14,7 @@ from .densify import (DensifyResult, densify_and_prune, densify_and_prune_torch,
                       reset_opacity)
 from .heatmap import (QuickHeatStream, heat_frames, heat_plan, jet_lut, mean_relevancy_maps,  # noqa: F401
                       summed_similarity_maps)
+from .lang_loss import language_l1_loss  # noqa: F401
 from .mask_nms import (NmsResult, PackedMasks, build_seg_maps, mask_nms, mask_pair_counts,  # noqa: F401
                        masks_update, pack_masks)
 from .photo_loss import l1_ssim, photometric_loss  # noqa: F401
@@ -27,7 +28,7 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "set_deterministic", "relevancy_maps", "similarity_maps", "query_plan", "QuickRelevancyStream",
            "smooth_maps", "segment_maps", "localize_maps", "hits", "SegmentResult", "LocalizeResult",
            "summed_similarity_maps", "mean_relevancy_maps", "heat_frames", "jet_lut", "heat_plan", "QuickHeatStream",
-           "photometric_loss", "l1_ssim", "densify_tensors", "densify_and_prune", "densify_and_prune_torch", "reset_opacity",
+           "photometric_loss", "l1_ssim", "language_l1_loss", "densify_tensors", "densify_and_prune", "densify_and_prune_torch", "reset_opacity",
            "DensifyResult", "assign_codes", "kmeans_step", "quantize", "fit_codebooks",
            "ResidualVectorQuantizationWithClustering", "pack_masks", "mask_pair_counts", "mask_nms", "masks_update",
            "build_seg_maps", "PackedMasks", "NmsResult", "mask_boxes", "clip_tiles", "mask2segmap",

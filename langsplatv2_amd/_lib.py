@@ -134,7 +134,7 @@ EXPORTS = ("lsr_forward", "lsr_backward", "lsr_mark_visible", "lsr_quick_decode"
            "lsr_quick_query_run", "lsr_quick_heat_plan_bytes", "lsr_quick_heat_prepare", "lsr_quick_heat_run",
            "lsr_heat_frame", "lsr_query_post_workspace_bytes", "lsr_query_smooth", "lsr_query_mask",
            "lsr_quick_pack_codes", "lsr_topk_code_forward",
-           "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_photo_loss_forward", "lsr_photo_loss_backward",
+           "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_lang_l1_forward", "lsr_lang_l1_backward", "lsr_photo_loss_forward", "lsr_photo_loss_backward",
            "lsr_kmeans_workspace_bytes", "lsr_kmeans_prepare", "lsr_kmeans_assign", "lsr_kmeans_update",
            "lsr_mask_nms_workspace_bytes", "lsr_mask_pack", "lsr_mask_pair_counts", "lsr_mask_nms_select",
            "lsr_mask_segmaps", "lsr_mask_boxes", "lsr_clip_tiles",
@@ -222,6 +222,11 @@ def load(path: str | None = None):
     lib.lsr_lang_loss_backward.argtypes = [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp,
                                            ALLOC_FN, _vp, _vp]
     lib.lsr_lang_loss_backward.restype = ctypes.c_int
+    lib.lsr_lang_l1_forward.argtypes = [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, ALLOC_FN, _vp, _vp]
+    lib.lsr_lang_l1_forward.restype = ctypes.c_int
+    lib.lsr_lang_l1_backward.argtypes = [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp,
+                                         ALLOC_FN, _vp, _vp]
+    lib.lsr_lang_l1_backward.restype = ctypes.c_int
     lib.lsr_photo_loss_forward.argtypes = [_vp, _vp, _ci, _ci, _ci, _vp, _vp, ALLOC_FN, _vp, _vp]
     lib.lsr_photo_loss_forward.restype = ctypes.c_int
     lib.lsr_photo_loss_backward.argtypes = [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]

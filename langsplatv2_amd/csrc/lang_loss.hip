@@ -454,4 +454,386 @@ hipError_t launch_lang_loss(const float* wmap, const float* cb, int Df, int H, i
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// The L1 loss of the same step (train.py:157-167 with --l1_loss, with or
+// without --normalize), behind lsr_lang_l1_forward / lsr_lang_l1_backward:
+//   u_p  = f_p                      or   a_p f_p,  a_p = 1/(|f_p| + 1e-10)
+//   loss = (1/(Df P)) sum_p m_p sum_d |u_pd - g_pd|,   g_p = FEAT[s_p]
+// |u - g| does not factor through the code space, so each wave forms f for
+// 64 pixels in blocks of 16 features on the exact-f32 MFMA (the weight tile
+// is the B operand in the output layout, as above), compares the block with
+// the FEAT rows of its pixels while it is in registers and drops it.  n_p =
+// |f_p| comes from the Gram matrix (sqrt(w.Gw), as the cosine forward), so
+// a_p is known before the first block.  The backward recomputes each block
+// with the same instruction sequence (the same sign at every element), forms
+//   dL/df_pd = c_p a_p (sign_pd - [n_p > 0] (t_p/n_p) f_pd),
+//   c_p = m_p gscale/(Df P),  t_p = sum_d u_pd sign_pd  (forward's stats;
+//   without --normalize a = 1 and the second term is absent)
+// and contracts it twice while it is there: over its 16 features into the
+// tile's dL/dw (the block is the B operand as it stands) and over the tile's
+// 64 pixels into the block's 64 x 16 slice of dL/dCB (the block transposed
+// through wave-private LDS).  The dL/dCB accumulators stay in registers: the
+// four waves of a workgroup take the same pixels and a quarter of the feature
+// blocks each (at most L1_CH = 4 per sweep over the pixels, 64 accumulator
+// registers; Df = 512 takes two sweeps, the second adds into dL/dw; with 8 and
+// one sweep the kernel spills more and is slower), their
+// partial dL/dw tiles meet in LDS (where the weight tile also lies, as the A
+// operand of the pixel contraction), the per-workgroup dL/dCB partials in a
+// second kernel, in a fixed order.  Pixels are tiled flat: tile t = pixels
+// 64t .. 64t + 63.
+
+#define L1_TS 68            // LDS row stride of the transposed gradient block
+#define L1_NORM_EPS 1e-10f  // train.py:159
+#ifndef L1_CH
+#define L1_CH 4             // feature blocks per wave and sweep (4 against 8, profiles/lang_l1_ab.json)
+#endif
+static_assert(L1_CH >= 1 && L1_CH <= 8, "L1_CH: 16 accumulator registers per block, at most 128");
+#define L1_WG 256           // workgroups of the backward
+
+struct L1Tile {
+    bool inp[4];
+    size_t pix[4];   // pixel (pb, li) = 64 t + 16 pb + li
+    int sp[4];       // segment id, -1 = masked / outside
+    __device__ __forceinline__ L1Tile(int64_t t, size_t HW, const int32_t* seg, int S, int li)
+    {
+#pragma unroll
+        for (int pb = 0; pb < 4; pb++) {
+            const size_t p = (size_t)t * 64 + pb * 16 + li;
+            inp[pb] = p < HW;
+            pix[pb] = inp[pb] ? p : 0;
+            const int s = inp[pb] ? seg[pix[pb]] : -1;
+            sp[pb] = (s >= 0 && s < S) ? s : -1;
+        }
+    }
+};
+
+__device__ __forceinline__ void l1_load_tile(const float* __restrict__ wmap, size_t HW, const L1Tile& tl, int lg,
+                                             float (&Wt)[LL_KB][4][4])
+{
+#pragma unroll
+    for (int kb = 0; kb < LL_KB; kb++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++) {
+                const float v = wmap[(size_t)(kb * 16 + 4 * lg + r) * HW + tl.pix[pb]];   // pix = 0 outside: in bounds
+                Wt[kb][r][pb] = tl.inp[pb] ? v : 0.f;
+            }
+}
+
+// F[pb][r] = f[db*16 + 4lg + r][pixel (pb, li)]: A = CB^T rows db*16 + li in
+// the tile's K-order.  Forward and backward both come through here, so both
+// see the same f bit for bit.
+__device__ __forceinline__ void l1_fblock(const float* __restrict__ cb, int Df, int db, int lg, int li,
+                                          const float (&Wt)[LL_KB][4][4], f32x4l (&F)[4])
+{
+    float a[LL_KB][4];
+#pragma unroll
+    for (int kb = 0; kb < LL_KB; kb++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) a[kb][r] = cb[(size_t)(kb * 16 + 4 * lg + r) * Df + db * 16 + li];
+#pragma unroll
+    for (int pb = 0; pb < 4; pb++) F[pb] = f32x4l{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < LL_KB; kb++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++)
+                F[pb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kb][r], Wt[kb][r][pb], F[pb], 0, 0, 0);
+}
+
+__device__ __forceinline__ float4 l1_grow(const float* __restrict__ feat, int Df, int s, int db, int lg)
+{
+    return s >= 0 ? *reinterpret_cast<const float4*>(feat + (size_t)s * Df + db * 16 + 4 * lg)
+                  : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// u - g in one rounding (a = 1 without --normalize), the same in both passes
+__device__ __forceinline__ float l1_diff(float a, float f, float g) { return fmaf(a, f, -g); }
+
+// G = CB CB^T alone (k_lang_prep with no segment rows)
+static void l1_gram(const float* cb, int Df, float* G, hipStream_t st)
+{
+    k_lang_prep<<<LL_K, 256, 0, st>>>(cb, nullptr, 0, Df, G, nullptr, nullptr);
+}
+
+// Forward.  stats (2, P): n_p and t_p, written with --normalize only.
+__global__ void __launch_bounds__(64) k_lang_l1_fwd(const float* __restrict__ wmap, size_t HW,
+                                                    const float* __restrict__ cb, int Df,
+                                                    const int32_t* __restrict__ seg, const float* __restrict__ feat,
+                                                    int S, int normalize, const float* __restrict__ G,
+                                                    float* __restrict__ stats, double* __restrict__ part)
+{
+    const int lane = threadIdx.x, lg = lane >> 4, li = lane & 15;
+    const int64_t NT = (int64_t)((HW + 63) / 64);
+    const int64_t t0 = NT * blockIdx.x / gridDim.x, t1 = NT * (blockIdx.x + 1) / gridDim.x;
+    const int ndb = Df / 16;
+    double total = 0.0;
+    for (int64_t t = t0; t < t1; t++) {
+        const L1Tile tl(t, HW, seg, S, li);
+        float Wt[LL_KB][4][4];
+        l1_load_tile(wmap, HW, tl, lg, Wt);
+        float a[4] = {1.f, 1.f, 1.f, 1.f}, nrm[4] = {0.f, 0.f, 0.f, 0.f};
+        if (normalize) {
+            float pn[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kb = 0; kb < LL_KB; kb++) {
+                f32x4l Y[4];
+                ll_gw_rows_upper(G, kb, lg, li, Wt, Y);
+#pragma unroll
+                for (int pb = 0; pb < 4; pb++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) pn[pb] = fmaf(Wt[kb][r][pb], Y[pb][r], pn[pb]);
+            }
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++) {
+                float vn = pn[pb];
+                vn += __shfl_xor(vn, 16, 64);
+                vn += __shfl_xor(vn, 32, 64);
+                nrm[pb] = sqrtf(fmaxf(vn, 0.f));
+                a[pb] = 1.f / (nrm[pb] + L1_NORM_EPS);
+            }
+        }
+        float acc = 0.f, tp[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int db = 0; db < ndb; db++) {
+            f32x4l F[4];
+            l1_fblock(cb, Df, db, lg, li, Wt, F);
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++) {
+                if (tl.sp[pb] < 0) continue;
+                const float4 g4 = l1_grow(feat, Df, tl.sp[pb], db, lg);
+                const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const float d = l1_diff(a[pb], F[pb][r], gg[r]);
+                    acc += fabsf(d);
+                    const float u = a[pb] * F[pb][r];
+                    tp[pb] += d > 0.f ? u : (d < 0.f ? -u : 0.f);
+                }
+            }
+        }
+        total += (double)acc;
+        if (normalize) {
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++) {
+                float vt = tp[pb];
+                vt += __shfl_xor(vt, 16, 64);
+                vt += __shfl_xor(vt, 32, 64);
+                if (lg == 0 && tl.inp[pb]) {
+                    stats[tl.pix[pb]] = nrm[pb];
+                    stats[HW + tl.pix[pb]] = vt;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) total += __shfl_xor(total, m, 64);
+    if (lane == 0) part[blockIdx.x] = total;
+}
+
+// loss = (sum of the per-wave sums) / (Df P), summed in index order
+__global__ void __launch_bounds__(256) k_lang_l1_total(const double* __restrict__ part, int n, double denom,
+                                                       float* __restrict__ loss)
+{
+    __shared__ double sh[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m) sh[threadIdx.x] += sh[threadIdx.x + m];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = (float)(sh[0] / denom);
+}
+
+// Backward.  Wave wv of the workgroup owns feature blocks d0 + wv*ch .. of
+// each pass (sweep over the pixels) of 4*L1_CH blocks; cpart is this
+// workgroup's (K, Df) partial of dL/dCB.
+__global__ void __launch_bounds__(256, 1) k_lang_l1_bwd(const float* __restrict__ wmap, size_t HW,
+                                                        const float* __restrict__ cb, int Df,
+                                                        const int32_t* __restrict__ seg,
+                                                        const float* __restrict__ feat, int S, int normalize,
+                                                        const float* __restrict__ stats,
+                                                        const float* __restrict__ gscale, float* __restrict__ gw,
+                                                        float* __restrict__ cpart)
+{
+    __shared__ float sD[4][16 * L1_TS];      // per wave: the gradient block, [feature][pixel]
+    __shared__ float sW[LL_K * L1_TS];       // the weight tile, [code][pixel]
+    __shared__ float4 sR[4][4][64];          // per wave: one code block of its dL/dw partial, [r][lane] over pb
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, lg = lane >> 4, li = lane & 15;
+    const int64_t NT = (int64_t)((HW + 63) / 64);
+    const int64_t t0 = NT * blockIdx.x / gridDim.x, t1 = NT * (blockIdx.x + 1) / gridDim.x;
+    const int ndb = Df / 16;
+    const float c0 = gscale[0] / ((float)Df * (float)HW);
+    float* myD = sD[wv];
+    float* cp = cpart + (size_t)blockIdx.x * LL_K * Df;
+
+    for (int pass0 = 0; pass0 < ndb; pass0 += 4 * L1_CH) {
+        const int nb = min(4 * L1_CH, ndb - pass0), ch = (nb + 3) / 4;
+        const int d0 = pass0 + wv * ch, d1 = min(pass0 + nb, d0 + ch);
+        f32x4l dC[L1_CH][LL_KB];
+#pragma unroll
+        for (int j = 0; j < L1_CH; j++)
+#pragma unroll
+            for (int kt = 0; kt < LL_KB; kt++) dC[j][kt] = f32x4l{0.f, 0.f, 0.f, 0.f};
+
+        for (int64_t t = t0; t < t1; t++) {
+            const L1Tile tl(t, HW, seg, S, li);
+            float Wt[LL_KB][4][4];
+            l1_load_tile(wmap, HW, tl, lg, Wt);
+            // the same tile in LDS, the A operand of the pixel contraction (wave wv stores code block wv;
+            // the last tile's readers are past the barriers of its dL/dw exchange)
+#pragma unroll
+            for (int kb = 0; kb < LL_KB; kb++) {
+                if (kb != wv) continue;
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+#pragma unroll
+                    for (int pb = 0; pb < 4; pb++) sW[(kb * 16 + 4 * lg + r) * L1_TS + pb * 16 + li] = Wt[kb][r][pb];
+            }
+            __syncthreads();
+            float a[4], ca[4], q[4];
+#pragma unroll
+            for (int pb = 0; pb < 4; pb++) {
+                const bool m = tl.sp[pb] >= 0;
+                const float n = (m && normalize) ? stats[tl.pix[pb]] : 0.f;
+                const float tt = (m && normalize) ? stats[HW + tl.pix[pb]] : 0.f;
+                a[pb] = normalize ? 1.f / (n + L1_NORM_EPS) : 1.f;
+                ca[pb] = m ? c0 * a[pb] : 0.f;
+                q[pb] = n > 0.f ? tt / n : 0.f;
+            }
+            f32x4l GW[LL_KB][4];
+#pragma unroll
+            for (int kb = 0; kb < LL_KB; kb++)
+#pragma unroll
+                for (int pb = 0; pb < 4; pb++) GW[kb][pb] = f32x4l{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+            for (int j = 0; j < L1_CH; j++) {
+                const int db = d0 + j;
+                if (db >= d1) continue;   // wave-uniform
+                f32x4l F[4];
+                l1_fblock(cb, Df, db, lg, li, Wt, F);
+                f32x4l D[4];
+#pragma unroll
+                for (int pb = 0; pb < 4; pb++) {
+                    const float4 g4 = l1_grow(feat, Df, tl.sp[pb], db, lg);
+                    const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const float d = l1_diff(a[pb], F[pb][r], gg[r]);
+                        const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+                        D[pb][r] = ca[pb] * fmaf(-q[pb], F[pb][r], sg);
+                        myD[(4 * lg + r) * L1_TS + pb * 16 + li] = D[pb][r];
+                    }
+                }
+                // dL/dw rows kb*16 + 4lg + r' += CB[kb*16 + li][db*16 + 4lg + r] D[4lg + r][pixel]
+#pragma unroll
+                for (int kb = 0; kb < LL_KB; kb++) {
+                    const float4 c4 = *reinterpret_cast<const float4*>(cb + (size_t)(kb * 16 + li) * Df + db * 16 + 4 * lg);
+                    const float cc[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+#pragma unroll
+                        for (int pb = 0; pb < 4; pb++)
+                            GW[kb][pb] = __builtin_amdgcn_mfma_f32_16x16x4f32(cc[r], D[pb][r], GW[kb][pb], 0, 0, 0);
+                }
+                wave_lds_fence();
+                // dL/dCB[kt*16 + 4lg + r][db*16 + li] += w[kt*16 + li][pixel 4s + lg] D[li][pixel 4s + lg]
+#pragma unroll
+                for (int s = 0; s < 16; s++) {
+                    const float b = myD[li * L1_TS + 4 * s + lg];
+#pragma unroll
+                    for (int kt = 0; kt < LL_KB; kt++)
+                        dC[j][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(sW[(kt * 16 + li) * L1_TS + 4 * s + lg], b,
+                                                                         dC[j][kt], 0, 0, 0);
+                }
+                wave_lds_fence();
+                __builtin_amdgcn_sched_barrier(0);   // one block's loads and temporaries at a time
+            }
+
+            // the four waves' dL/dw partials, one code block at a time: wave wv sums row r = wv in wave order
+#pragma unroll
+            for (int kb = 0; kb < LL_KB; kb++) {
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+                    sR[wv][r][lane] = make_float4(GW[kb][0][r], GW[kb][1][r], GW[kb][2][r], GW[kb][3][r]);
+                __syncthreads();
+                float4 v = sR[0][wv][lane];
+#pragma unroll
+                for (int w = 1; w < 4; w++) {
+                    const float4 x = sR[w][wv][lane];
+                    v.x += x.x, v.y += x.y, v.z += x.z, v.w += x.w;
+                }
+                const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int pb = 0; pb < 4; pb++) {
+                    if (!tl.inp[pb]) continue;
+                    float* o = gw + (size_t)(kb * 16 + 4 * lg + wv) * HW + tl.pix[pb];
+                    *o = pass0 ? *o + vv[pb] : vv[pb];
+                }
+                __syncthreads();
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < L1_CH; j++) {
+            const int db = d0 + j;
+            if (db >= d1) continue;
+#pragma unroll
+            for (int kt = 0; kt < LL_KB; kt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) cp[(size_t)(kt * 16 + 4 * lg + r) * Df + db * 16 + li] = dC[j][kt][r];
+        }
+    }
+}
+
+// dL/dCB = the workgroups' partials summed in workgroup order
+__global__ void __launch_bounds__(256) k_lang_l1_dcb(const float* __restrict__ cpart, int n, int KD,
+                                                     float* __restrict__ dcb)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= KD) return;
+    float s = 0.f;
+    for (int w = 0; w < n; w++) s += cpart[(size_t)w * KD + i];
+    dcb[i] = s;
+}
+
+static int l1_fwd_waves(int64_t P) { return (int)std::max<int64_t>(1, std::min<int64_t>((P + 63) / 64, 2048)); }
+static int l1_bwd_groups(int64_t P) { return (int)std::max<int64_t>(1, std::min<int64_t>((P + 63) / 64, L1_WG)); }
+
+size_t lang_l1_workspace_bytes(int Df, int W, int H)
+{
+    const int64_t P = (int64_t)W * H;
+    // G, the forward's per-wave sums (double), the backward's dL/dCB partials, pixel stats (2 planes)
+    return sizeof(float) * ((size_t)LL_K * LL_K + 2 * (size_t)l1_fwd_waves(P) +
+                            (size_t)l1_bwd_groups(P) * LL_K * Df + 2 * (size_t)P + 64);
+}
+
+hipError_t launch_lang_l1(const float* wmap, const float* cb, int Df, int H, int W, const int32_t* seg,
+                          const float* feat, int S, int normalize, const float* gscale, float* loss, float* gw,
+                          float* dcb, float* stats, float* ws, hipStream_t st)
+{
+    const size_t P = (size_t)W * H;
+    const int nw = l1_fwd_waves((int64_t)P), ng = l1_bwd_groups((int64_t)P);
+    float* G = ws;
+    double* part = reinterpret_cast<double*>(G + LL_K * LL_K);   // 16 KiB in: 8-byte aligned
+    float* cpart = reinterpret_cast<float*>(part + nw);
+    float* own_stats = cpart + (size_t)ng * LL_K * Df;
+    if (normalize) l1_gram(cb, Df, G, st);
+    if (!gw) {
+        k_lang_l1_fwd<<<nw, 64, 0, st>>>(wmap, P, cb, Df, seg, feat, S, normalize, G, stats ? stats : own_stats, part);
+        if (loss) k_lang_l1_total<<<1, 256, 0, st>>>(part, nw, (double)Df * (double)P, loss);
+        return hipGetLastError();
+    }
+    if (normalize && !stats) {   // backward without the forward's stats: recompute them
+        stats = own_stats;
+        k_lang_l1_fwd<<<nw, 64, 0, st>>>(wmap, P, cb, Df, seg, feat, S, normalize, G, stats, part);
+    }
+    k_lang_l1_bwd<<<ng, 256, 0, st>>>(wmap, P, cb, Df, seg, feat, S, normalize, stats, gscale, gw, cpart);
+    k_lang_l1_dcb<<<(LL_K * Df + 255) / 256, 256, 0, st>>>(cpart, ng, LL_K * Df, dcb);
+    return hipGetLastError();
+}
+
 }  // namespace lsr

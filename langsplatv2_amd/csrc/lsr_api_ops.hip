@@ -299,6 +299,33 @@ int lsr_lang_loss_backward(const float* weight_map, const float* codebooks, int 
     return LSR_OK;
 }
 
+int lsr_lang_l1_forward(const float* weight_map, const float* codebooks, int K, int Df, int H, int W,
+                        const int32_t* seg, const float* features, int S, int normalize, float* loss,
+                        float* pixel_stats, lsr_alloc_fn alloc, void* alloc_ctx, void* stream)
+{
+    LSR_TRY(lang_loss_args(weight_map, codebooks, K, Df, H, W, seg, features, S));
+    if ((!loss && !pixel_stats) || !alloc) return LSR_EINVAL;
+    float* ws = (float*)alloc(alloc_ctx, lang_l1_workspace_bytes(Df, W, H), LSR_BUF_LOSS);
+    if (!ws) return LSR_ENOMEM;
+    LSR_HIP(launch_lang_l1(weight_map, codebooks, Df, H, W, seg, features, S, normalize != 0, nullptr, loss, nullptr,
+                           nullptr, pixel_stats, ws, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_lang_l1_backward(const float* weight_map, const float* codebooks, int K, int Df, int H, int W,
+                         const int32_t* seg, const float* features, int S, int normalize, const float* pixel_stats,
+                         const float* grad_loss, float* grad_weight_map, float* grad_codebooks, lsr_alloc_fn alloc,
+                         void* alloc_ctx, void* stream)
+{
+    LSR_TRY(lang_loss_args(weight_map, codebooks, K, Df, H, W, seg, features, S));
+    if (!grad_loss || !grad_weight_map || !grad_codebooks || !alloc) return LSR_EINVAL;
+    float* ws = (float*)alloc(alloc_ctx, lang_l1_workspace_bytes(Df, W, H), LSR_BUF_LOSS);
+    if (!ws) return LSR_ENOMEM;
+    LSR_HIP(launch_lang_l1(weight_map, codebooks, Df, H, W, seg, features, S, normalize != 0, grad_loss, nullptr,
+                           grad_weight_map, grad_codebooks, const_cast<float*>(pixel_stats), ws, (hipStream_t)stream));
+    return LSR_OK;
+}
+
 int lsr_photo_loss_forward(const float* image, const float* gt, int planes, int H, int W, float* out, float* partials,
                            lsr_alloc_fn alloc, void* alloc_ctx, void* stream)
 {

@@ -284,6 +284,14 @@ hipError_t launch_lang_loss(const float* wmap, const float* cb, int Df, int H, i
                             const float* feat, int S, const float* gscale, float* loss, float* gw, float* dcb,
                             float* stats, float* ws, hipStream_t st);
 
+// lang_loss.hip, the L1 pair (--l1_loss, optionally --normalize): normalize != 0 divides f_p by |f_p| + 1e-10
+size_t lang_l1_workspace_bytes(int Df, int W, int H);
+// gw == nullptr: forward (loss and, with normalize, the per-pixel stats (2, H, W) = |f_p|, sum_d u_pd sign_pd);
+// else dL/dweight_map and dL/dcodebooks scaled by *gscale, from the forward's stats (recomputed when nullptr)
+hipError_t launch_lang_l1(const float* wmap, const float* cb, int Df, int H, int W, const int32_t* seg,
+                          const float* feat, int S, int normalize, const float* gscale, float* loss, float* gw,
+                          float* dcb, float* stats, float* ws, hipStream_t st);
+
 // photo_loss.hip: L1 + SSIM of (planes, H, W) images (planes H W < 2^31)
 struct PhotoTaps {
     float w[11];   // the normalised 1-D window (sigma 1.5), formed in double and rounded once

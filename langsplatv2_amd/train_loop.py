@@ -367,18 +367,19 @@ def render_language(cam: dict, ls: LanguageState, bg: torch.Tensor) -> dict:
 
 def language_view_loss(pkg: dict, ls: LanguageState, seg: torch.Tensor, features: torch.Tensor,
                        normalize: bool = False, cos: bool = True, l1: bool = False,
-                       iteration: int = 0) -> torch.Tensor:
+                       iteration: int = 0, fused_l1: bool = False) -> torch.Tensor:
     """train.py:151-167: the decoded feature map of level layer_idx =
     min(int(iteration / 10000 * layer_num), layer_num - 1) (always 0 with the
     single codebook level this phase trains, see LanguageState) against the
     view's ground truth gathered from its (S, Df) table by its segment map,
     under the --normalize / --cos_loss / --l1_loss flags (default: train.sh's
-    --cos_loss alone, the fused kernel)."""
+    --cos_loss alone, the fused kernel; `fused_l1` sends --l1_loss through
+    its fused kernel too, see language_feature_loss)."""
     from .lang_loss import language_feature_loss
     layer_num = ls.codebooks.shape[0]
     layer_idx = min(int(iteration / 10000 * layer_num), layer_num - 1)
     return language_feature_loss(pkg["language_feature_weight_map"], ls.codebooks, seg, features,
-                                 layer_idx=layer_idx, normalize=normalize, cos=cos, l1=l1)
+                                 layer_idx=layer_idx, normalize=normalize, cos=cos, l1=l1, fused_l1=fused_l1)
 
 
 class LanguageTrainer:
@@ -387,10 +388,11 @@ class LanguageTrainer:
     bucket, every rank steps its replica (= --accum_iter R on one GPU)."""
 
     def __init__(self, ls: LanguageState, bg: torch.Tensor, group=None, fused_adam: bool = True,
-                 normalize: bool = False, cos_loss: bool = True, l1_loss: bool = False):
+                 normalize: bool = False, cos_loss: bool = True, l1_loss: bool = False, fused_l1: bool = False):
         self.ls = ls
         self.bg = bg
-        self.loss_flags = dict(normalize=normalize, cos=cos_loss, l1=l1_loss)   # train.py --normalize / --cos_loss / --l1_loss
+        # train.py --normalize / --cos_loss / --l1_loss; fused_l1: the L1 term's fused kernel (opt-in)
+        self.loss_flags = dict(normalize=normalize, cos=cos_loss, l1=l1_loss, fused_l1=fused_l1)
         self.opt = ls.optimizer(fused=fused_adam)
         self.exchange = dp.ViewShardedExchange(ls.params(), with_stats=False, group=group,
                                                names=list(LANG_PARAM_NAMES))
