@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_mask_boxes, lsr_clip_tiles;
+#define LSR_ABI_VERSION 12  /* 12, additive (no bump): lsr_quick_semantic_plan_bytes / _prepare / _run, lsr_semantic_merge / _confusion;
+                               12, additive (no bump): lsr_mask_boxes, lsr_clip_tiles;
                                12, additive (no bump): lsr_mask_nms_workspace_bytes, lsr_mask_pack / _pair_counts / _nms_select / _segmaps;
                                12, additive (no bump): lsr_kmeans_workspace_bytes / _prepare / _assign / _update;
                                12, additive (no bump): lsr_photo_loss_forward / _backward;
@@ -295,6 +296,55 @@ int lsr_quick_query_prepare(const float* codebooks, const float* pos, const floa
                             int n_pos, int n_neg, void* plan, void* stream);
 int lsr_quick_query_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int n_pos,
                         int n_neg, int H, int W, int mode, float scale, float eps, float* out, void* stream);
+
+/* Fused open-vocabulary label maps of the quick path: what the reference
+ * computes from the decoded, normalised (L, H, W, Df) map with
+ * OpenCLIPNetwork.get_semantic_map (eval/openclip_encoder.py:82-94), taken
+ * straight from the weight map — the Df-dim map is never written.  labels
+ * (n_labels, Df) and neg (n_neg, Df) are the text embeddings (fp32 device
+ * pointers, used as given); the columns are the reference's
+ * cat([semantic_embeds, neg_embeds]).  Per level and pixel, with
+ * s_j = f . e_j / (|f| + eps):
+ *   labels_out (L, H, W) int32   argmax_j s_j, the lowest column on exact ties
+ *                                (torch.argmax on the CPU), -1 when a negative wins;
+ *   scores_out (L, H, W) fp32    1 / sum_j exp(scale (s_j - s_max)), the
+ *                                reference's softmax(scale s) at its arg-max;
+ *                                optional (NULL: not computed, and the labels
+ *                                are the same bits).
+ * An all-zero pixel gives label 0 and score 1 / (n_labels + n_neg) exactly.
+ * lsr_quick_semantic_prepare writes the (codebooks, label set) part into a
+ * caller-owned device buffer of lsr_quick_semantic_plan_bytes bytes
+ * (0 = unsupported shape), valid until the codebooks or the embeddings change;
+ * n_labels and n_neg of a run must be the plan's.  K must be 64, Df a multiple
+ * of 16, n_labels >= 1, n_neg >= 0, n_labels + n_neg <= 256, scale >= 0 (the
+ * reference's is 10).
+ *
+ * lsr_semantic_merge: out (H, W) int32 = per pixel the label of the level
+ * with the largest score, the lowest level on ties; level (H, W) uint8 = that
+ * level, optional.  The rule is this library's own: the reference returns the
+ * per-level maps only.  L <= 255.
+ *
+ * lsr_semantic_confusion: counts (P, n_classes, n_classes + 1) int64, zeroed
+ * by the call; counts[p][g][c] = the pixels with gt (H, W) int32 == g and
+ * plane p of pred (P, H, W) int32 == c, column n_classes collecting pred == -1.
+ * Pixels with gt outside [0, n_classes) (ignore labels such as 255 or -1) or
+ * pred outside [-1, n_classes) are skipped.  n_classes <= 256, P <= 65535,
+ * H * W < 2^31.  Integer sums: exact and bit-identical from run to run.
+ *
+ * LSR_EINVAL: a NULL required pointer, an unknown layout, a negative count or a
+ * negative or NaN scale; LSR_EUNSUPPORTED: K != 64, Df % 16 != 0, more than
+ * 256 columns or classes, a misaligned pixel-major map, a shape out of range;
+ * L, H, W or P = 0: LSR_OK with nothing launched.  Additive to ABI 12. */
+size_t lsr_quick_semantic_plan_bytes(int L, int K, int Df, int n_labels, int n_neg);
+int lsr_quick_semantic_prepare(const float* codebooks, const float* labels, const float* neg, int L, int K, int Df,
+                               int n_labels, int n_neg, void* plan, void* stream);
+int lsr_quick_semantic_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int n_labels,
+                           int n_neg, int H, int W, float scale, float eps, int32_t* labels_out, float* scores_out,
+                           void* stream);
+int lsr_semantic_merge(const int32_t* labels, const float* scores, int L, int H, int W, int32_t* out, uint8_t* level,
+                       void* stream);
+int lsr_semantic_confusion(const int32_t* pred, const int32_t* gt, int P, int H, int W, int n_classes, int64_t* counts,
+                           void* stream);
 
 /* Post-process of the relevancy maps (eval_lerf.py:104-200; eval_3d_ovs.py:
  * 102-107, 215-260) on planes = L * n_prompt independent (H, W) fp32 planes

@@ -21,6 +21,8 @@ from .photo_loss import l1_ssim, photometric_loss  # noqa: F401
 from .query import QuickRelevancyStream, query_plan, relevancy_maps, similarity_maps  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: F401
                          rasterize_gaussians)
+from .semantic import (QuickSemanticStream, SemanticScores, get_semantic_map, label_confusion,  # noqa: F401
+                       merge_levels, semantic_maps, semantic_plan, semantic_scores)
 from .segment import (LocalizeResult, SegmentResult, hits, localize_maps, segment_maps,  # noqa: F401
                       smooth_maps)
 
@@ -32,4 +34,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "DensifyResult", "assign_codes", "kmeans_step", "quantize", "fit_codebooks",
            "ResidualVectorQuantizationWithClustering", "pack_masks", "mask_pair_counts", "mask_nms", "masks_update",
            "build_seg_maps", "PackedMasks", "NmsResult", "mask_boxes", "clip_tiles", "mask2segmap",
-           "segment_tiles_and_maps"]
+           "segment_tiles_and_maps", "semantic_maps", "semantic_plan", "get_semantic_map", "merge_levels",
+           "label_confusion", "semantic_scores", "SemanticScores", "QuickSemanticStream"]

@@ -131,7 +131,8 @@ ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c
 
 EXPORTS = ("lsr_forward", "lsr_backward", "lsr_mark_visible", "lsr_quick_decode", "lsr_quick_decode_plan_bytes",
            "lsr_quick_decode_prepare", "lsr_quick_decode_run", "lsr_quick_query_plan_bytes", "lsr_quick_query_prepare",
-           "lsr_quick_query_run", "lsr_quick_heat_plan_bytes", "lsr_quick_heat_prepare", "lsr_quick_heat_run",
+           "lsr_quick_query_run", "lsr_quick_semantic_plan_bytes", "lsr_quick_semantic_prepare",
+           "lsr_quick_semantic_run", "lsr_semantic_merge", "lsr_semantic_confusion", "lsr_quick_heat_plan_bytes", "lsr_quick_heat_prepare", "lsr_quick_heat_run",
            "lsr_heat_frame", "lsr_query_post_workspace_bytes", "lsr_query_smooth", "lsr_query_mask",
            "lsr_quick_pack_codes", "lsr_topk_code_forward",
            "lsr_topk_code_backward", "lsr_topk_code_backward_sparse", "lsr_knn_dist2", "lsr_lang_loss_forward", "lsr_lang_loss_backward", "lsr_lang_l1_forward", "lsr_lang_l1_backward", "lsr_photo_loss_forward", "lsr_photo_loss_backward",
@@ -182,6 +183,17 @@ def load(path: str | None = None):
     lib.lsr_quick_query_run.argtypes = [_vp, ctypes.c_int, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float,
                                                                                       _vp, _vp]
     lib.lsr_quick_query_run.restype = ctypes.c_int
+    lib.lsr_quick_semantic_plan_bytes.argtypes = [ctypes.c_int] * 5
+    lib.lsr_quick_semantic_plan_bytes.restype = ctypes.c_size_t
+    lib.lsr_quick_semantic_prepare.argtypes = [_vp, _vp, _vp] + [ctypes.c_int] * 5 + [_vp, _vp]
+    lib.lsr_quick_semantic_prepare.restype = ctypes.c_int
+    lib.lsr_quick_semantic_run.argtypes = [_vp, ctypes.c_int, _vp] + [ctypes.c_int] * 6 + [ctypes.c_float,
+                                                                                         ctypes.c_float, _vp, _vp, _vp]
+    lib.lsr_quick_semantic_run.restype = ctypes.c_int
+    lib.lsr_semantic_merge.argtypes = [_vp, _vp] + [ctypes.c_int] * 3 + [_vp, _vp, _vp]
+    lib.lsr_semantic_merge.restype = ctypes.c_int
+    lib.lsr_semantic_confusion.argtypes = [_vp, _vp] + [ctypes.c_int] * 4 + [_vp, _vp]
+    lib.lsr_semantic_confusion.restype = ctypes.c_int
     lib.lsr_quick_heat_plan_bytes.argtypes = [ctypes.c_int] * 5
     lib.lsr_quick_heat_plan_bytes.restype = ctypes.c_size_t
     lib.lsr_quick_heat_prepare.argtypes = [_vp, _vp, _vp] + [ctypes.c_int] * 5 + [_vp, _vp]

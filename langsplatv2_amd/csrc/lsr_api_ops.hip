@@ -192,6 +192,72 @@ int lsr_quick_query_run(const float* weight_map, int weight_layout, const void* 
     return LSR_OK;
 }
 
+// the semantic entries' shape checks: LSR_EINVAL for a count out of its domain,
+// then LSR_EUNSUPPORTED for a shape the kernel does not take
+static int semantic_args(int L, int K, int Df, int n_labels, int n_neg)
+{
+    if (L < 0 || K <= 0 || Df <= 0 || n_labels < 1 || n_neg < 0) return LSR_EINVAL;
+    if (K != 64 || (Df % 16) != 0 || (int64_t)n_labels + n_neg > 256) return LSR_EUNSUPPORTED;
+    return LSR_OK;
+}
+
+size_t lsr_quick_semantic_plan_bytes(int L, int K, int Df, int n_labels, int n_neg)
+{
+    if (semantic_args(L, K, Df, n_labels, n_neg) != LSR_OK) return 0;
+    return quick_semantic_plan_bytes(L, K, n_labels, n_neg);
+}
+
+int lsr_quick_semantic_prepare(const float* codebooks, const float* labels, const float* neg, int L, int K, int Df,
+                               int n_labels, int n_neg, void* plan, void* stream)
+{
+    LSR_TRY(semantic_args(L, K, Df, n_labels, n_neg));
+    if (L == 0) return LSR_OK;
+    if (!codebooks || !labels || (n_neg > 0 && !neg) || !plan) return LSR_EINVAL;
+    LSR_HIP(launch_quick_semantic_prepare(codebooks, labels, neg, L, K, Df, n_labels, n_neg, plan,
+                                          (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_quick_semantic_run(const float* weight_map, int weight_layout, const void* plan, int L, int K, int n_labels,
+                           int n_neg, int H, int W, float scale, float eps, int32_t* labels_out, float* scores_out,
+                           void* stream)
+{
+    if (H < 0 || W < 0 || !layout_ok(weight_layout)) return LSR_EINVAL;
+    // the arg-max of softmax(scale s) is the arg-max of s only for scale >= 0
+    if (!(scale >= 0.f)) return LSR_EINVAL;
+    LSR_TRY(semantic_args(L, K, 16, n_labels, n_neg));
+    if (L == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!weight_map || !plan || !labels_out) return LSR_EINVAL;
+    const bool hwc = weight_layout == LSR_LAYOUT_HWC;
+    // the pixel-major map is read in 16-B pieces
+    if (hwc && misaligned16(weight_map)) return LSR_EUNSUPPORTED;
+    LSR_HIP(launch_quick_semantic_run(weight_map, hwc, plan, L, K, n_labels, n_neg, H, W, scale, eps, labels_out,
+                                      scores_out, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_semantic_merge(const int32_t* labels, const float* scores, int L, int H, int W, int32_t* out, uint8_t* level,
+                       void* stream)
+{
+    if (L < 0 || H < 0 || W < 0) return LSR_EINVAL;
+    if (L > 255 || (int64_t)H * W >= (1ll << 31)) return LSR_EUNSUPPORTED;   // the level is written as uint8
+    if (L == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!labels || !scores || !out) return LSR_EINVAL;
+    LSR_HIP(launch_semantic_merge(labels, scores, L, H, W, out, level, (hipStream_t)stream));
+    return LSR_OK;
+}
+
+int lsr_semantic_confusion(const int32_t* pred, const int32_t* gt, int P, int H, int W, int n_classes, int64_t* counts,
+                           void* stream)
+{
+    if (P < 0 || H < 0 || W < 0 || n_classes < 1) return LSR_EINVAL;
+    if (n_classes > 256 || P > 65535 || (int64_t)H * W >= (1ll << 31)) return LSR_EUNSUPPORTED;
+    if (P == 0 || H == 0 || W == 0) return LSR_OK;
+    if (!pred || !gt || !counts) return LSR_EINVAL;
+    LSR_HIP(launch_semantic_confusion(pred, gt, P, H, W, n_classes, counts, (hipStream_t)stream));
+    return LSR_OK;
+}
+
 size_t lsr_quick_heat_plan_bytes(int L, int K, int Df, int n_pos, int n_neg)
 {
     if (codebook_args(L, K, Df) != LSR_OK || L > 3 || n_pos < 1 || n_neg < 0 || n_pos + n_neg > 64) return 0;

@@ -246,9 +246,24 @@ hipError_t launch_quick_query_prepare(const float* cb, const float* pos, const f
                                       int n_pos, int n_neg, void* ws, hipStream_t st);
 hipError_t launch_quick_query_run(const float* wmap, bool hwc, const void* ws, int L, int K, int n_pos, int n_neg,
                                   int H, int W, bool relevancy, float scale, float eps, float* out, hipStream_t st);
-// the f32 projections P (L, K, ncp) = CB_l E^T the heat plan shares: columns = the negatives, the positives, zeros
+// the f32 projections P (L, K, ncp) = CB_l E^T the heat and semantic plans share: columns = the negatives, the
+// positives, zeros
 void launch_query_project(const float* cb, const float* pos, const float* neg, int L, int K, int Df, int n_pos,
                           int n_neg, int ncp, float* P, hipStream_t st);
+
+// quick_semantic.hip: fused label maps (K = 64, n_lab + n_neg <= 256; columns: the labels, then the negatives;
+// scores == nullptr: labels only), their level merge and the confusion counts of an evaluation
+size_t quick_semantic_plan_bytes(int L, int K, int n_lab, int n_neg);
+hipError_t launch_quick_semantic_prepare(const float* cb, const float* lab, const float* neg, int L, int K, int Df,
+                                         int n_lab, int n_neg, void* ws, hipStream_t st);
+hipError_t launch_quick_semantic_run(const float* wmap, bool hwc, const void* ws, int L, int K, int n_lab, int n_neg,
+                                     int H, int W, float scale, float eps, int32_t* labels, float* scores,
+                                     hipStream_t st);
+hipError_t launch_semantic_merge(const int32_t* labels, const float* scores, int L, int H, int W, int32_t* out,
+                                 uint8_t* level, hipStream_t st);
+// counts (P, C, C + 1) int64, zeroed here
+hipError_t launch_semantic_confusion(const int32_t* pred, const int32_t* gt, int P, int H, int W, int C,
+                                     int64_t* counts, hipStream_t st);
 
 // quick_heat.hip: the viewer's maps (summed-level cosine / mean relevancy, (n_pos, H, W); K = 64, L <= 3,
 // n_pos + n_neg <= 64) and the colour stage (gate, curve, table, blend with rgb, uint8 (planes, H, W, 3))

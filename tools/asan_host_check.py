@@ -202,6 +202,53 @@ TABLE = [
     ("lsr_heat_frame", (None, None, None, None, 2, 4, 0, 0, 0.22, 0.02, 0.0, None, None), OK),
     ("lsr_heat_frame", (None, None, None, None, 1, 4, 4, 0, 0.22, 0.02, 0.5, None, None), EINVAL),
     ("lsr_heat_frame", (P, P, None, P, 1, 4, 4, 0, 0.22, 0.02, 0.5, None, None), EINVAL),
+    # lsr_quick_semantic_prepare(cb, labels, neg, L, K, Df, n_labels, n_neg, plan, stream)
+    ("lsr_quick_semantic_prepare", (None, None, None, 3, 64, 512, 0, 4, None, None), EINVAL),
+    ("lsr_quick_semantic_prepare", (None, None, None, 3, 64, 512, 5, -1, None, None), EINVAL),
+    ("lsr_quick_semantic_prepare", (None, None, None, -1, 64, 512, 5, 4, None, None), EINVAL),
+    ("lsr_quick_semantic_prepare", (None, None, None, 3, 64, 0, 5, 4, None, None), EINVAL),
+    ("lsr_quick_semantic_prepare", (None, None, None, 3, 32, 512, 5, 4, None, None), EUNSUP),
+    ("lsr_quick_semantic_prepare", (None, None, None, 3, 64, 17, 5, 4, None, None), EUNSUP),
+    ("lsr_quick_semantic_prepare", (None, None, None, 3, 64, 512, 253, 4, None, None), EUNSUP),
+    ("lsr_quick_semantic_prepare", (None, None, None, 3, 32, 512, 0, 4, None, None), EINVAL),   # both
+    ("lsr_quick_semantic_prepare", (None, None, None, 0, 64, 512, 5, 4, None, None), OK),
+    ("lsr_quick_semantic_prepare", (None, None, None, 3, 64, 512, 5, 4, None, None), EINVAL),
+    ("lsr_quick_semantic_prepare", (P, P, None, 3, 64, 512, 5, 4, P, None), EINVAL),    # negatives without their rows
+    # lsr_quick_semantic_run(wmap, layout, plan, L, K, n_labels, n_neg, H, W, scale, eps, labels, scores, stream)
+    ("lsr_quick_semantic_run", (None, 2, None, 3, 64, 5, 4, 4, 4, 10.0, 1e-10, None, None, None), EINVAL),
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 64, 5, 4, 4, 4, -1.0, 1e-10, None, None, None), EINVAL),
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 64, 5, 4, 4, 4, NAN, 1e-10, None, None, None), EINVAL),
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 64, 0, 4, 4, 4, 10.0, 1e-10, None, None, None), EINVAL),
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 64, 5, 4, -1, 4, 10.0, 1e-10, None, None, None), EINVAL),
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 32, 5, 4, 4, 4, 10.0, 1e-10, None, None, None), EUNSUP),
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 64, 253, 4, 4, 4, 10.0, 1e-10, None, None, None), EUNSUP),
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 32, 5, 4, 4, 4, -1.0, 1e-10, None, None, None), EINVAL),   # both
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 64, 253, 4, 0, 4, 10.0, 1e-10, None, None, None), EUNSUP),   # before the no-op
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 64, 5, 4, 0, 4, 10.0, 1e-10, None, None, None), OK),
+    ("lsr_quick_semantic_run", (None, 1, None, 0, 64, 5, 0, 4, 4, 0.0, 1e-10, None, None, None), OK),
+    ("lsr_quick_semantic_run", (None, 0, None, 3, 64, 5, 4, 4, 4, 10.0, 1e-10, None, None, None), EINVAL),
+    ("lsr_quick_semantic_run", (P, 0, P, 3, 64, 5, 4, 4, 4, 10.0, 1e-10, None, P, None), EINVAL),      # scores without labels
+    ("lsr_quick_semantic_run", (ODD, 1, P, 3, 64, 5, 4, 4, 4, 10.0, 1e-10, P, None, None), EUNSUP),
+    # lsr_semantic_merge(labels, scores, L, H, W, out, level, stream)
+    ("lsr_semantic_merge", (None, None, -1, 4, 4, None, None, None), EINVAL),
+    ("lsr_semantic_merge", (None, None, 256, 4, 4, None, None, None), EUNSUP),
+    ("lsr_semantic_merge", (None, None, 3, 65536, 65536, None, None, None), EUNSUP),
+    ("lsr_semantic_merge", (None, None, 256, 4, -1, None, None, None), EINVAL),   # both
+    ("lsr_semantic_merge", (None, None, 0, 4, 4, None, None, None), OK),
+    ("lsr_semantic_merge", (None, None, 3, 4, 0, None, None, None), OK),
+    ("lsr_semantic_merge", (None, None, 3, 4, 4, None, None, None), EINVAL),
+    ("lsr_semantic_merge", (P, P, 3, 4, 4, None, P, None), EINVAL),
+    # lsr_semantic_confusion(pred, gt, P, H, W, n_classes, counts, stream)
+    ("lsr_semantic_confusion", (None, None, 3, 4, 4, 0, None, None), EINVAL),
+    ("lsr_semantic_confusion", (None, None, -1, 4, 4, 21, None, None), EINVAL),
+    ("lsr_semantic_confusion", (None, None, 3, 4, 4, 257, None, None), EUNSUP),
+    ("lsr_semantic_confusion", (None, None, 65536, 4, 4, 21, None, None), EUNSUP),
+    ("lsr_semantic_confusion", (None, None, 3, 65536, 65536, 21, None, None), EUNSUP),
+    ("lsr_semantic_confusion", (None, None, 0, 4, 4, 257, None, None), EUNSUP),   # before the no-op
+    ("lsr_semantic_confusion", (None, None, 0, 4, 4, 21, None, None), OK),
+    ("lsr_semantic_confusion", (None, None, 3, 0, 4, 256, None, None), OK),
+    ("lsr_semantic_confusion", (None, None, 3, 4, 4, 21, None, None), EINVAL),
+    ("lsr_semantic_confusion", (P, P, 3, 4, 4, 21, None, None), EINVAL),
     # lsr_query_smooth(rel, planes, H, W, kernel, avg, blend, stats, loc, workspace, stream)
     ("lsr_query_smooth", (None, 2, 4, 4, 4, None, None, None, None, None, None), EINVAL),
     ("lsr_query_smooth", (None, 2, 4, 4, 0, None, None, None, None, None, None), EINVAL),
@@ -420,6 +467,11 @@ for args, some in [((3, 64, 512, 1, 1), True), ((3, 64, 512, 64, 0), True), ((3,
                    ((3, 64, 17, 1, 1), False), ((3, 64, 0, 1, 1), False), ((-1, 64, 512, 1, 1), False),
                    ((3, 64, 512, 0, 1), False), ((3, 64, 512, 1, -1), False), ((3, 64, 512, 33, 32), False)]:
     assert (lib.lsr_quick_query_plan_bytes(*args) > 0) == some, args
+    calls += 1
+for args, some in [((3, 64, 512, 1, 0), True), ((3, 64, 512, 252, 4), True), ((3, 32, 512, 5, 4), False),
+                   ((3, 64, 17, 5, 4), False), ((3, 64, 512, 0, 4), False), ((3, 64, 512, 253, 4), False),
+                   ((-1, 64, 512, 5, 4), False)]:
+    assert (lib.lsr_quick_semantic_plan_bytes(*args) > 0) == some, args
     calls += 1
 for args, some in [((3, 64, 512, 1, 0), True), ((1, 64, 16, 60, 4), True), ((4, 64, 512, 1, 1), False),
                    ((3, 32, 512, 1, 1), False), ((3, 64, 500, 1, 1), False), ((3, 64, 512, 61, 4), False),
